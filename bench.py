@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- DDPM reverse-sampling throughput on MSR-80c (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs the W warm-up steps (plus ~0.3 s, at least one call, of the timed K-step call untimed: it captures
+the step graphs the timed call replays and brings the clock up), times ONE sample() call of exactly K steps and prints the result
+line.  `--dump-outputs DIR` writes what that call returned (rank 0's y_0, B x 80 float32) as DIR/y0.npy; the inputs are
+seeded, so two builds of the project compare output for output.  `--full` adds everything else below (box probes, the
+exact-float32 re-run, the training leg, the roofline's eager profiled re-run, the other BASELINE configs, the CPU baseline) and
+times 7 consecutive K-step calls (median).
 
 A *step* is one reverse step of DDPM.sample (classifier_free_MSR.py:124-137) over one synthetic batch:
 2 denoiser forwards (unconditional + conditional) + CFG combine + ancestral update (+ the global renorm on the first
@@ -17,7 +24,7 @@ on v_mfma_f32_32x32x16_f16 (`diffsg_amd/csrc/dsg_split.hpp`), which measures as 
 exact v_mfma_f32_32x32x2_f32 path (1.3e-6 vs 1.4e-6 worst relative error on the parity cases) and is what `dtype`
 "f32(2xf16-split MFMA, f32 accumulate)" names.  `--precision f32` times the exact-f32 MFMA path instead.
 
-Printed JSON (rank 0): the driver contract keys plus
+Printed JSON (rank 0): the driver contract keys plus, with --full,
   roofline      dominant kernel (the proj_dim-wide up blocks): mean launch time from HIP events recorded around each launch
                 on the launch stream in a second, eager run of the same K steps.  `achieved` = EXECUTED matrix-core FLOP per
                 second: the split path issues 3 v_mfma_f32_32x32x16_f16 per float32 product, so 3 x the algorithmic FLOP
@@ -381,6 +388,44 @@ def train_leg(dev, dist, rank, world, B, steps, barrier, warmup=8, use_graph=Tru
             "bucket_checksum_equal": bool(eq), "bucket_checksum": csum}
 
 
+def headline(a, world, K, W, B, dt, rep_ms, ev):
+    """The result line of a plain run: the driver contract keys and what describes the timed K-step call(s)."""
+    step_ms = dt / K * 1e3
+    return {
+        "metric": "ddpm_reverse_sample_steps_per_sec_msr80c", "value": world * K / dt, "unit": "steps/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": step_ms, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32(2xf16-split MFMA, f32 accumulate)" if a.precision == "split_f16" else "f32", "data": "synthetic",
+        "config": {"workload": f"MSR-80c CFG reverse sampling, batch {B} x D=C=80 per GPU, UNet1D(proj 128, dims "
+                               f"(64,32,16,8), n_blocks 2), omega={a.omega:g}, device Philox noise; rows sharded, no collective",
+                   "batch_per_gpu": B, "solution_dim": 80, "parallelism": f"rows x{world}"},
+        "row_steps_per_s": world * K * B / dt,
+        # `value` = K / the median of R consecutive timed K-step calls (R = 1 unless --repeats / --full); their spread rides along
+        "repeats": {"n": len(rep_ms), "ms_per_step_min": min(rep_ms), "ms_per_step_median": step_ms, "ms_per_step_max": max(rep_ms),
+                    "ms_per_step_all": [round(v, 4) for v in rep_ms]},
+        "ranks_seen": ev["ranks_seen"], "per_rank_steps_per_s": ev["per_rank_steps_per_s"],
+    }
+
+
+DUMP_LIMIT_BYTES = 60 << 20      # under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy, float32, of what the timed call returned.  An array above the budget is written as a fixed sample of
+    its rows (the same rows in every run: a seeded permutation, sorted), so that two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu()
+        row_bytes = x[0].numel() * 4 if x.dim() > 1 and x.shape[0] else 0
+        if x.numel() * 4 > budget and row_bytes:
+            keep = min(x.shape[0], budget // row_bytes)
+            idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            x = x[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,8 +443,15 @@ def main():
     ap.add_argument("--no-f32-exact", action="store_true", help="skip the exact-float32 re-run of the same K steps")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE config-2 sub-record (MSR-3c, 8192 rows, T = 1000)")
     ap.add_argument("--warm-seconds", type=float, default=0.3, help="untimed clock warm-up before the timed steps")
-    ap.add_argument("--repeats", type=int, default=7, help="consecutive timed K-step sample() calls; `value` is the median (each is exactly K steps)")
+    ap.add_argument("--repeats", type=int, default=None, help="consecutive timed K-step sample() calls; `value` is the median (each is exactly K "
+                                                              "steps).  Default: 1, or 7 with --full")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: box probes, exact-float32 re-run, "
+                                                        "training leg, roofline (eager profiled re-run), other BASELINE configs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed sample() call returned (rank 0) as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 7 if a.full else 1
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)                      # never returns; nothing has touched the GPU yet
@@ -439,17 +491,21 @@ def main():
         torch.cuda.synchronize()
 
     ddpm_w.sample(cond, a.omega, seed=1)  # W untimed warm-up steps (also builds tables, captures the step graph)
-    # a box that was idle ramps its clocks over some tens of milliseconds: keep the GPU busy (untimed, same W-step call) for
-    # ~0.3 s before the timed region so that the K timed steps are measured at the sustained clock
-    torch.cuda.synchronize()
-    t_warm = time.perf_counter()
-    while time.perf_counter() - t_warm < a.warm_seconds:
-        ddpm_w.sample(cond, a.omega, seed=1)
-        torch.cuda.synchronize()
     # the K-step schedule's coefficient table (4 floats per step, a function of the registered schedule buffers only) is built
     # on an object's first call and cached on it; the timed object is fresh only because the warm-up uses its own W-step schedule
     ddpm_k._coef_table()
-    box = box_calibrate()                 # fixed MFMA / copy probes on this box, right before the timed region (also keeps the clock up)
+    # a box that was idle ramps its clocks over some tens of milliseconds, and the first replays of a graph run slower than later
+    # ones: keep the GPU busy with the timed call itself (untimed, at least once) for ~0.3 s before the timed region, so that the K
+    # timed steps are measured at the sustained clock.  Its first call also captures the step graphs of the K-step decomposition
+    # (captured lazily, per run length: dsg_api.hip, sample_impl) that the W-step warm-up did not need: no timed call pays for one
+    torch.cuda.synchronize()
+    t_warm = time.perf_counter()
+    while True:
+        ddpm_k.sample(cond, a.omega, seed=2)
+        torch.cuda.synchronize()
+        if time.perf_counter() - t_warm >= a.warm_seconds:
+            break
+    box = box_calibrate() if a.full else None   # fixed MFMA / copy probes on this box, right before the timed region (also keeps the clock up)
     from diffsg_amd import parallel as par
     # R consecutive timed calls of exactly K steps each, every one between barrier + synchronize; `value` is the MEDIAN call (the
     # first call of a process and a box's clock excursions fall out of it), min / max ride along in `repeats`
@@ -465,9 +521,18 @@ def main():
     dt = ev["max_seconds"]
     rep_ms = [e["max_seconds"] / K * 1e3 for e in evs]
     assert torch.isfinite(y0).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"y0": y0})
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(headline(a, world, K, W, B, dt, rep_ms, ev)))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     box_after = box_calibrate()
 
-    # the same K steps on the exact-float32 kernels (v_mfma_f32_32x32x2_f32), so that a strict-fp32 figure always sits beside the
+    # the same K steps on the exact-float32 kernels (v_mfma_f32_32x32x2_f32), so that a strict-fp32 figure sits beside the
     # split-f16 one.  Untimed warm-up first: the precision switch drops the captured step graphs.
     f32_exact = None
     if a.precision == "split_f16" and not a.no_f32_exact:
@@ -532,19 +597,9 @@ def main():
                   "interleaved with the MFMA stream)" if panel else
                   "k_wide128_h<linear-shortcut> (4 tiles per workgroup, weight planes through an LDS ring)") if large
                  else "k_resblock_c<128,linear-shortcut>") if split else "k_resblock<128,linear-shortcut>"
-        out = {
-            "metric": "ddpm_reverse_sample_steps_per_sec_msr80c", "value": world * K / dt, "unit": "steps/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": step_ms, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32(2xf16-split MFMA, f32 accumulate)" if a.precision == "split_f16" else "f32", "data": "synthetic",
-            "config": {"workload": f"MSR-80c CFG reverse sampling, batch {B} x D=C=80 per GPU, UNet1D(proj 128, dims "
-                                   f"(64,32,16,8), n_blocks 2), omega={a.omega:g}, device Philox noise; rows sharded, no collective",
-                       "batch_per_gpu": B, "solution_dim": 80, "parallelism": f"rows x{world}"},
-            "row_steps_per_s": world * K * B / dt,
-            # `value` = K / the median of R consecutive timed K-step calls; the spread of the calls and this box's rates on four fixed
-            # probes ride along
-            "repeats": {"n": len(rep_ms), "ms_per_step_min": min(rep_ms), "ms_per_step_median": step_ms, "ms_per_step_max": max(rep_ms),
-                        "ms_per_step_all": [round(v, 4) for v in rep_ms]},
+        out = headline(a, world, K, W, B, dt, rep_ms, ev)
+        out.update({
+            # this box's rates on four fixed probes ride along
             "box": {"before": box, "after": box_after,
                     "probe": "dsg_box_calibrate, median of five 3-10 ms launches each, run right before and right after the timed calls: mfma_tflops = "
                              "dependent v_mfma_f32_32x32x16_f16 on every SIMD; mix_gslots = the same with 6 vector instructions behind every MFMA "
@@ -577,8 +632,7 @@ def main():
             # launch and the launches do not overlap their tails as they do inside the replayed graph, so these sum ABOVE ms_per_step;
             # `eager_profile_ms_per_step` is that run's own wall time per step (upper bounds, for ratios between operators)
             "op_ms_per_step": {r[0]: r[3] / K for r in prof}, "eager_profile_ms_per_step": eager_ms,
-            "ranks_seen": ev["ranks_seen"], "per_rank_steps_per_s": ev["per_rank_steps_per_s"],
-        }
+        })
         # The driver's parser keeps `roofline` and `cpu_baseline` whole and only the NAMES of other top-level keys: what a
         # strict reader needs sits INSIDE `roofline` -- the exact-float32 rate against SURVEY 8(d)'s 973-steps/s fp32 roof, the whole step
         # against the unit it runs on, its traffic, the training step, and every other BASELINE config under `roofline.configs`.

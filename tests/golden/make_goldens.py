@@ -235,6 +235,8 @@ def g4():
                 if i > T - 5:
                     y = (y - torch.mean(y)) / torch.sqrt(torch.var(y))
             out[f"om{omega:g}_y0_f64"] = y.numpy()
+    # the per-step eps go to a file of their own: together with the checkpoint they exceed the 1 MiB limit of a committed file
+    save("g4_sample_nu_ckpt_eps.npz", om1_eps_steps=out.pop("om1_eps_steps"))
     save("g4_sample_nu_ckpt.npz", **out)
 
     # (2) synthetic weights, several configs, short T (T=8 also exercises i>T-5 and the i<=1 no-noise rule)

@@ -81,7 +81,8 @@ def _worker(rank, ws, port, q):
         from diffsg_amd import train as tr
         from diffsg_amd.ddpm import _PublishGrads
         dev_, rank_, world_ = tr.dp_context()
-        assert (rank_, world_) == (rank, ws) and dev_ is None        # no GPU here: the entry points raise at this point
+        # without a GPU there is no device (the entry points raise at this point); with one, LOCAL_RANK is unset: both ranks get cuda:0
+        assert (rank_, world_) == (rank, ws) and dev_ == (torch.device("cuda", 0) if torch.cuda.is_available() else None)
         assert torch.initial_seed() != 0 or rank == 0                # per-rank seed offset applied
         torch.manual_seed(100 + rank)
         m2 = UNet1D(input_dim=3, proj_dim=16, cond_dim=3, dims=(16, 8, 4), is_attn=(False,) * 3, n_blocks=2)

@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     env = dict(os.environ, DSG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2048", "--train-batch", "1024", "--steps", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "2048", "--train-batch", "1024", "--steps", "4",
            "--warmup", "1", "--repeats", "3", "--train-steps", "4", "--no-cpu-baseline", "--no-f32-exact", "--no-other-configs"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,8 +1,11 @@
 """Pin the CPU oracle against vectors captured from the imported reference.
 
 The oracle issues the reference's ATen ops in the reference's order, so float32 results are expected to be
-bit-identical on the torch build that generated the goldens; the asserted tolerance is 2e-6 relative so that a
-different CPU / torch build (different GEMM blocking) still passes.
+bit-identical on the torch build that generated the goldens; the asserted tolerances cover a different CPU / torch build
+(different GEMM blocking and vector code paths).  Where a CPU's rounding moves a result past 2e-6 relative, the bar is
+about twice the worst spread measured across CPU code paths: the goldens' host (Intel, MKL AVX-512), an AMD EPYC host, and
+MKL's AVX2 / SSE4.2 / COMPATIBLE paths with ATen's vector or scalar kernels (MKL_ENABLE_INSTRUCTIONS, MKL_CBWR,
+ATEN_CPU_CAPABILITY).
 """
 import json
 import os
@@ -16,6 +19,8 @@ from oracle import ddpm_oracle as O
 from weights import CONFIGS
 
 RTOL = 2e-6
+# the denoiser forward and its module taps: up to 1.05e-5 across the CPU code paths above (3.4e-6 on the AMD EPYC host)
+RTOL_FWD = 2e-5
 
 
 def close(a, b, rtol=RTOL, atol=None):
@@ -50,13 +55,13 @@ def test_g2_unet_forward(gold, name, flavour, seed):
         taps = {}
         ts = torch.from_numpy(g["a_ts"])
         eps = O.unet_forward(p, plan, x, ts / int(g["a_T"]), cond, torch.from_numpy(g["a_mask"]), taps)
-        close(eps, g["a_eps"])
+        close(eps, g["a_eps"], rtol=RTOL_FWD)
         for k in g.files:
             if k.startswith("a_tap."):
-                close(taps[k[len("a_tap."):]], g[k])
+                close(taps[k[len("a_tap."):]], g[k], rtol=RTOL_FWD)
         t = torch.full((1, B), int(g["b_step"]), dtype=torch.int64) / 20
-        close(O.unet_forward(p, plan, x, t, cond, torch.zeros(B, 1)), g["b_eps"])
-        close(O.unet_forward(p, plan, x, t, cond, torch.ones(B, 1)), g["c_eps"])
+        close(O.unet_forward(p, plan, x, t, cond, torch.zeros(B, 1)), g["b_eps"], rtol=RTOL_FWD)
+        close(O.unet_forward(p, plan, x, t, cond, torch.ones(B, 1)), g["c_eps"], rtol=RTOL_FWD)
 
 
 @pytest.mark.parametrize("name", ["tiny", "nu3", "msr80"])
@@ -73,7 +78,8 @@ def test_g3_loss_and_grads(gold, name):
     for k, v in grads.items():
         if name == "tiny":
             ref = g["grad." + k]
-            assert np.abs(v.numpy() - ref).max() <= 2e-6 * gmax + 1e-6 * np.abs(ref).max(), k
+            # up to 2.4 x (2e-6 gmax + 1e-6 max|ref|) with ATen's scalar kernels: the bar is 5 x that
+            assert np.abs(v.numpy() - ref).max() <= 1e-5 * gmax + 5e-6 * np.abs(ref).max(), k
         else:
             nrm = float(torch.sqrt((v.double() ** 2).sum()))
             assert abs(nrm - float(g["gradnorm." + k])) <= 1e-5 * max(float(g["gradnorm." + k]), 1e-3 * gmax), k
@@ -94,12 +100,18 @@ def test_g4_sample_nu_checkpoint(gold):
     T = int(g["T"])
     bufs = O.schedule_buffers(1.0 - O.cosine_betas(T))
     cond, y_T, z = torch.from_numpy(g["cond"]), torch.from_numpy(g["y_T"]), _z_dict(g["z"], T)
-    for omega, tol in ((0.0, RTOL), (1.0, RTOL), (500.0, 1e-4)):
+    for omega in (0.0, 1.0, 500.0):
         trace = []
         y0 = O.ddpm_sample(p, plan, bufs, T, cond, omega, y_T, z, trace)
-        close(y0, g[f"om{omega:g}_y0"], rtol=tol)
+        if omega < 500.0:
+            close(y0, g[f"om{omega:g}_y0"])
+        else:
+            # omega = 500 amplifies a last-bit difference ~1e5-fold: two float32 evaluations of the same trajectory on different
+            # CPUs differ by up to 9.3e-3 (AMD EPYC vs the goldens' host).  Held to the float64 trajectory within the float32
+            # budget the reference's own float32 run is held to below (2e-2; the reference is at 2.6e-3)
+            close(y0, g["om500_y0_f64"], rtol=2e-2)
         if omega == 1.0:
-            close(np.stack([e.numpy() for _, _, e in trace]), g["om1_eps_steps"], rtol=1e-5)
+            close(np.stack([e.numpy() for _, _, e in trace]), gold("g4_sample_nu_ckpt_eps.npz")["om1_eps_steps"], rtol=1e-5)
     # known answer: less ratio 0.91359 on these rows at omega = 500
     y0 = torch.from_numpy(g["om500_y0"])
     Xs = cond.clone()
@@ -122,7 +134,8 @@ def test_g4_sample_nu_checkpoint(gold):
     b64 = O.schedule_buffers(1.0 - O.cosine_betas(T))  # buffers stay float32-valued, as registered
     b64 = {k: v.double() for k, v in b64.items()}
     y64 = O.ddpm_sample(p64, plan, b64, T, cond.double(), 500.0, y_T.double(), {i: v.double() for i, v in z.items()})
-    close(y64, g["om500_y0_f64"], rtol=1e-9)
+    # omega = 500 amplifies float64 rounding too: up to 4.7e-7 with MKL's AVX2 dgemm, 6.9e-12 on the AMD EPYC host
+    close(y64, g["om500_y0_f64"], rtol=1e-6)
 
 
 @pytest.mark.parametrize("name,T", [("tiny", 8), ("msr80", 6), ("msr3", 6), ("co3", 6), ("tiny", 3)])
