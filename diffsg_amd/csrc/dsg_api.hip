@@ -12,6 +12,7 @@
 #include "dsg_eval.hpp"
 #include "dsg_labelgen.hpp"
 #include "dsg_cogen.hpp"
+#include "dsg_nugen.hpp"
 #include "../../include/diffsg.h"
 
 #include <math.h>
@@ -2906,6 +2907,34 @@ int dsg_co_minlp_search(const double* params, const double* choices, int nch, do
     if (rows == 0) return 0;
     const CoGenConst cc{F_t, P_t, P_I, theta};
     hipLaunchKernelGGL(k_co_minlp, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, params, choices, nch, n, cc, Y, tolerable);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int dsg_noma_uav_search(const double* qs, const double* fs, int nfs, double* out, long long rows, double sigma_sq, double rou_0,
+                        double H, void* stream) {
+    if (!qs || !fs || !out) return fail("dsg_noma_uav_search: null pointer argument");
+    if (nfs < 3 || nfs > kNuMaxSolutions) return fail("dsg_noma_uav_search: nfs = %d table rows (must be in [3, %d])", nfs, kNuMaxSolutions);
+    if (rows < 0 || rows > 0x7fffffffLL) return fail("dsg_noma_uav_search: bad row count");
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    // small calls: short point runs, so that one sample still fills many CUs; large calls: long runs, fewer idle lanes at
+    // the end of each workgroup's list
+    const int tile_pts = rows < 64 ? 256 : kNuMaxTile;
+    const int tiles = (kNuGridPts + tile_pts - 1) / tile_pts;
+    const long long chunk = std::min<long long>(rows, 16384);   // pass-1 grid: chunk * tiles workgroups (< 2^32 work-items)
+    double* best_rate = nullptr;
+    HIPCK(hipMallocAsync(reinterpret_cast<void**>(&best_rate), (size_t)chunk * tiles * 16, s));
+    unsigned long long* best_key = reinterpret_cast<unsigned long long*>(best_rate + chunk * tiles);
+    const NuGenConst cc{sigma_sq, rou_0, H};
+    for (long long r0 = 0; r0 < rows; r0 += chunk) {
+        const long long n = std::min(chunk, rows - r0);
+        hipLaunchKernelGGL(k_nu_tiles, dim3((unsigned)(n * tiles)), dim3(kNuThreads), 0, s, qs + r0 * 6, fs, nfs, cc, tile_pts, tiles,
+                           best_rate, best_key);
+        hipLaunchKernelGGL(k_nu_pick, dim3((unsigned)n), dim3(kNuThreads), 0, s, qs + r0 * 6, fs, cc, tiles, best_rate, best_key,
+                           out + r0 * 6);
+    }
+    HIPCK(hipFreeAsync(best_rate, s));
     HIPCK(hipGetLastError());
     return 0;
 }

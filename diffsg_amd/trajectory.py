@@ -1,5 +1,6 @@
 """De-noising trajectory files (reference: datasets/sum_rate_trajectory_gen.py:25-51, datasets/co_trajectory_gen.py:20-59,
-ddpm_opt/classifier_free_NU.py:365-394) and the sum-rate dataset file (datasets/sum_rate_gen.py:9-14).
+ddpm_opt/classifier_free_NU.py:365-394) and the label files of the MSR and NU problems (datasets/sum_rate_gen.py:9-14,
+datasets/noma_uav_gen.py:173-182).
 
 The reference records the trajectory with two device-to-host copies per reverse step (MSR.py:139-141); here every step
 lands in a device-side ring inside the per-step graph (dsg_sample_rec) and comes back with ONE copy per `sample()` call.
@@ -94,3 +95,24 @@ def sum_rate_dataset_store(out_csv=None, sample_num=2000, M=80, W=20.0, g_range=
     pd.DataFrame(table).to_csv(out_csv, index=False, header=None)
     log("Data generation finished.")
     return table
+
+
+def nu_dataset_store(out_csv=None, sample_num=2500, P_sum=18, extend=False, ext_csv=None, qs=None, log=print):
+    """datasets/noma_uav_gen.py's __main__: `[users (6) | UAV x, y | powers (3) | rate]` per row, no header, under a name
+    `.._<P>mW_<N>samples.csv` so that `nu_data_load` reads P_sum from it.  Labels come from the device search
+    (labelgen.noma_uav_gen).  With `extend=True` the rows are also augmented (labelgen.dataset_extension, 3 copies) into
+    `ext_csv` (default: `.._<P>mW_extension.csv` next to it).  Returns the table, or (table, extension)."""
+    import os
+    from .labelgen import dataset_extension, noma_uav_gen
+    table = noma_uav_gen(sample_num, P_sum, qs=qs, log=log)
+    if out_csv is None:
+        out_csv = f"../datasets/3u_{int(P_sum)}mW_{table.shape[0]}samples.csv"
+    pd.DataFrame(table).to_csv(out_csv, index=False, header=None)
+    log("Data generation finished.")
+    if not extend:
+        return table
+    if ext_csv is None:
+        ext_csv = os.path.join(os.path.dirname(out_csv), f"3u_{int(P_sum)}mW_extension.csv")
+    ext = dataset_extension(out_csv)
+    pd.DataFrame(ext).to_csv(ext_csv, index=False, header=None)
+    return table, ext

@@ -240,6 +240,16 @@ int dsg_sum_rate_gen(const double* gs, double* schemes, double* rates, long long
 int dsg_co_minlp_search(const double* params, const double* choices, int nch, double* Y, int* tolerable, long long rows, int n,
                         double F_t, double P_t, double P_I, double theta, void* stream);
 
+/* ---- Label generator of the NU problem: the search of noma_uav_gen, datasets/noma_uav_gen.py (float64).
+ * qs [rows][6] = 3 user positions per sample (the reference draws them with numpy; the caller does); fs [nfs][3] the power
+ * table feasible_solution(P_sum) (smallest power first, drawn up by the caller), 3 <= nfs <= 16384.  Per sample, every point
+ * of the integer grid [0, 400]^2 inside the users' triangle (edges included) x every table row; out [rows][6] receives
+ * x, y | powers in user order | rate of the FIRST best (grid order, then table order), all zeros if no grid point is inside.
+ * The rate is the generator's own formula (interference = sum of whole table rows picked by the stronger users' indices),
+ * not the one of dsg_nu_rate.  sigma_sq, rou_0, H: 110, 60, 150 in the reference.  Stream-ordered. */
+int dsg_noma_uav_search(const double* qs, const double* fs, int nfs, double* out, long long rows, double sigma_sq, double rou_0,
+                        double H, void* stream);
+
 /* Measurement hooks for bench.py: the per-step operator list and a timed replay of one operator's kernel with HIP
  * events on `stream` (rows = B rows, both passes, as inside dsg_sample). */
 int dsg_op_count(const dsg_handle* h);
