@@ -2,7 +2,7 @@
 
 The module tree below exists only to own the parameters under the reference's state-dict keys (SURVEY.md 5.4:
 `feature_proj`, `time_emb.lin{1,2}`, `down.<i>.res.*` / `down.<i>.lin`, `middle.res{1,2}`, `up.<i>.res.*` /
-`up.<i>.lin`, `norm`, `final`) and to construct them in the reference's order, so a seeded construction gives the
+`up.<i>.lin`, `norm`, `final`; with is_attn / middle_attn also `down.<i>.attn.*`, `middle.attn.*`, `up.<i>.attn.*`) and to construct them in the reference's order, so a seeded construction gives the
 reference's initial weights and `load_state_dict(strict=True)` accepts the reference's checkpoints.  No arithmetic
 happens in Python: `forward` hands device pointers to libdiffsg_hip.so.
 """
@@ -48,29 +48,45 @@ class ResidualBlock(_ParamsOnly):
         self.cond_emb = nn.Linear(cond_dim, out_dim)
 
 
+class AttentionBlock(_ParamsOnly):
+    """UNetCF.py:98-121 with n_heads = 1, d_k = in_dim (the only form the reference's constructor builds).  On the (batch, 1, d)
+    input the softmax is identically 1: the library computes output(Wv x + bv) + x with Wv / bv = rows 2d:3d of `projection`
+    (csrc/dsg_attn.hpp); `norm` is registered, as in the reference, and never used."""
+
+    def __init__(self, in_dim):
+        super().__init__()
+        self.norm = nn.LayerNorm(in_dim)
+        self.projection = nn.Linear(in_dim, in_dim * 3)
+        self.output = nn.Linear(in_dim, in_dim)
+
+
 class _ResHolder(_ParamsOnly):
-    def __init__(self, in_dim, out_dim, time_dim, cond_dim):
+    def __init__(self, in_dim, out_dim, time_dim, cond_dim, has_attn=False):
         super().__init__()
         self.res = ResidualBlock(in_dim, out_dim, time_dim, cond_dim)
+        if has_attn:                       # (the reference registers nn.Identity() otherwise: no parameters, no state-dict keys)
+            self.attn = AttentionBlock(out_dim)
 
 
 class DownBlock(_ResHolder):
-    """UNetCF.py:160-168."""
+    """UNetCF.py:160-179: res, then attn."""
 
 
 class UpBlock(_ResHolder):
-    """UNetCF.py:182-192: the block sees cat(x, skip), i.e. in_dim + out_dim features."""
+    """UNetCF.py:182-203: the block sees cat(x, skip), i.e. in_dim + out_dim features; res, then attn."""
 
-    def __init__(self, in_dim, out_dim, time_dim, cond_dim):
-        super().__init__(in_dim + out_dim, out_dim, time_dim, cond_dim)
+    def __init__(self, in_dim, out_dim, time_dim, cond_dim, has_attn=False):
+        super().__init__(in_dim + out_dim, out_dim, time_dim, cond_dim, has_attn)
 
 
 class MiddleBlock(_ParamsOnly):
-    """UNetCF.py:206-215."""
+    """UNetCF.py:206-227: res1, attn, res2."""
 
-    def __init__(self, dim, time_dim, cond_dim):
+    def __init__(self, dim, time_dim, cond_dim, has_attn=False):
         super().__init__()
         self.res1 = ResidualBlock(dim, dim, time_dim, cond_dim)
+        if has_attn:
+            self.attn = AttentionBlock(dim)
         self.res2 = ResidualBlock(dim, dim, time_dim, cond_dim)
 
 
@@ -164,33 +180,37 @@ class UNet1D(nn.Module):
                  middle_attn=False,
                  n_blocks=2):
         super().__init__()
-        if any(is_attn) or middle_attn:
-            raise NotImplementedError("AttentionBlock is never enabled by the reference's call sites and is not built")
-        self.cfg = dict(input_dim=int(input_dim), proj_dim=int(proj_dim), cond_dim=int(cond_dim),
-                        dims=tuple(int(d) for d in dims), n_blocks=int(n_blocks))
-        time_dim = proj_dim * 4
         n_res = len(dims)
+        is_attn = tuple(bool(a) for a in is_attn)
+        if len(is_attn) < n_res:
+            if any(is_attn):
+                raise ValueError(f"is_attn has {len(is_attn)} entries for {n_res} resolutions")
+            is_attn = (False,) * n_res     # the all-False default is accepted for any depth, as before
+        self.cfg = dict(input_dim=int(input_dim), proj_dim=int(proj_dim), cond_dim=int(cond_dim),
+                        dims=tuple(int(d) for d in dims), n_blocks=int(n_blocks),
+                        is_attn=is_attn[:n_res], middle_attn=bool(middle_attn))
+        time_dim = proj_dim * 4
         self.feature_proj = nn.Linear(input_dim, proj_dim)
         self.time_emb = TimeEmbedding(time_dim)
 
         down = []
         width = proj_dim
         for i in range(n_res):
-            down += [DownBlock(width, width, time_dim, cond_dim) for _ in range(n_blocks)]
+            down += [DownBlock(width, width, time_dim, cond_dim, is_attn[i]) for _ in range(n_blocks)]
             down.append(Downsample(width, dims[i]))
             width = dims[i]
             if i == n_res - 1:
-                down += [DownBlock(width, width, time_dim, cond_dim) for _ in range(n_blocks)]
+                down += [DownBlock(width, width, time_dim, cond_dim, is_attn[i]) for _ in range(n_blocks)]
         self.down = nn.ModuleList(down)
-        self.middle = MiddleBlock(width, time_dim, cond_dim)
+        self.middle = MiddleBlock(width, time_dim, cond_dim, bool(middle_attn))
         up = []
         for i in reversed(range(n_res)):
-            up += [UpBlock(width, width, time_dim, cond_dim) for _ in range(n_blocks + 1)]
+            up += [UpBlock(width, width, time_dim, cond_dim, is_attn[i]) for _ in range(n_blocks + 1)]
             nxt = dims[i - 1] if i > 0 else proj_dim
             up.append(Upsample(width, nxt))
             width = nxt
             if i == 0:
-                up += [UpBlock(width, width, time_dim, cond_dim) for _ in range(n_blocks + 1)]
+                up += [UpBlock(width, width, time_dim, cond_dim, is_attn[i]) for _ in range(n_blocks + 1)]
         self.up = nn.ModuleList(up)
         self.norm = nn.LayerNorm(width)
         self.final = nn.Linear(width, input_dim)
@@ -222,7 +242,11 @@ class UNet1D(nn.Module):
             for i, v in enumerate(c["dims"]):
                 d.dims[i] = v
             with torch.cuda.device(params[0][1].device):
-                hd = L.dsg_create(ctypes.byref(d))
+                if any(c["is_attn"]) or c["middle_attn"]:
+                    flags = (ctypes.c_int * len(c["dims"]))(*[int(a) for a in c["is_attn"]])
+                    hd = L.dsg_create_attn(ctypes.byref(d), flags, int(c["middle_attn"]))
+                else:
+                    hd = L.dsg_create(ctypes.byref(d))
             if not hd:
                 raise RuntimeError("libdiffsg_hip: " + L.dsg_last_error().decode())
             nat.handle = hd

@@ -149,6 +149,7 @@ _lib = None
 _SIGS = {
     # name: (restype, argtypes)
     "dsg_create": (ctypes.c_void_p, [ctypes.POINTER(UNetDesc)]),
+    "dsg_create_attn": (ctypes.c_void_p, [ctypes.POINTER(UNetDesc), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "dsg_destroy": (None, [ctypes.c_void_p]),
     "dsg_last_error": (ctypes.c_char_p, []),
     "dsg_param_count": (ctypes.c_int, [ctypes.c_void_p]),

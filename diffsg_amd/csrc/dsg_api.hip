@@ -8,6 +8,7 @@
 #include "dsg_panel.hpp"
 #include "dsg_res64.hpp"
 #include "dsg_tile.hpp"
+#include "dsg_attn.hpp"
 #include "dsg_train_split.hpp"
 #include "dsg_eval.hpp"
 #include "dsg_labelgen.hpp"
@@ -93,6 +94,15 @@ struct LinOpP {            // feature_proj / Down/Upsample / final
     size_t du, rs;         // final only (training)
 };
 
+struct AttnP {             // AttentionBlock on a sequence of length 1 (UNetCF.py:98-157, dsg_attn.hpp)
+    int N = 0;
+    NormP norm;            // registered, never called by the reference's forward: its gradients are exact zeros
+    LinearP proj, out;     // projection (d -> 3d: only rows 2d:3d = Wv reach the output), output (d -> d)
+    size_t Wvp = 0, bvp = 0, Wop = 0, bop = 0, WvT = 0, WoT = 0;   // packed (arena offsets, floats)
+    size_t Wvh = 0, Woh = 0;   // fp16-split planes (>= 64 wide: k_attn_h)
+    size_t v = 0, dv = 0;  // training workspace (per-tile float offsets): v = Wv x + bv of the forward, dv = Wo^T dy of the backward
+};
+
 struct TensorInfo {
     int width;
     size_t data_off, stats_off;   // forward workspace, per-tile float offsets
@@ -100,10 +110,10 @@ struct TensorInfo {
     bool is_skip;
 };
 
-enum OpKind { OP_PROJ, OP_RES, OP_LIN, OP_FINAL };
+enum OpKind { OP_PROJ, OP_RES, OP_LIN, OP_FINAL, OP_ATTN };
 struct Op {
     OpKind kind;
-    int p;          // index into res / lin
+    int p;          // index into res / lin / attn
     int in0, in1;   // tensor ids (-1: none)
     int out;        // tensor id (-1 for final)
     std::string name;
@@ -131,6 +141,7 @@ struct dsg_handle {
     long long total_params = 0;
     std::vector<ResP> res;
     std::vector<LinOpP> lin;
+    std::vector<AttnP> attn;     // dsg_create_attn; empty for a net without attention: nothing below changes then
     std::vector<TensorInfo> tensors;
     std::vector<Op> ops;
     size_t per_tile_floats = 0;
@@ -320,6 +331,15 @@ int add_res(dsg_handle* h, const std::string& prefix, int in0, int in1, int N) {
     h->res.push_back(r);
     return (int)h->res.size() - 1;
 }
+int add_attn(dsg_handle* h, const std::string& prefix, int N) {
+    AttnP a;
+    a.N = N;
+    a.norm = add_norm(h, prefix + ".norm", N);
+    a.proj = add_linear(h, prefix + ".projection", N, 3 * N);
+    a.out = add_linear(h, prefix + ".output", N, N);
+    h->attn.push_back(a);
+    return (int)h->attn.size() - 1;
+}
 int add_tensor(dsg_handle* h, int width, bool is_skip) {
     TensorInfo t;
     t.width = width;
@@ -385,6 +405,13 @@ void carve(dsg_handle* h) {
         const size_t KSc = (size_t)(CG + 1) / 2;
         for (auto& r : h->res) r.Wch = c.take((size_t)cdiv(r.N, 32) * KSc * 128 * 4);
     }
+    for (auto& a : h->attn) {   // behind everything else: the arena of a net without attention is laid out as before
+        const int NT = cdiv(a.N, 32), NG = groups_of(a.N);
+        a.Wvp = c.take((size_t)NT * NG * 256); a.bvp = c.take(NT * 32);
+        a.Wop = c.take((size_t)NT * NG * 256); a.bop = c.take(NT * 32);
+        a.WvT = c.take((size_t)NT * NG * 256); a.WoT = c.take((size_t)NT * NG * 256);
+        if (a.N >= 64) { a.Wvh = c.take((size_t)NT * ((NG + 1) / 2) * 128 * 4); a.Woh = c.take((size_t)NT * ((NG + 1) / 2) * 128 * 4); }
+    }
     h->zero_off = c.take(128);
     h->arena_floats = c.off;
     for (auto& r : h->res) { r.ce_off = h->ce_per_tile; h->ce_per_tile += (size_t)groups_of(r.N) * 256; }
@@ -402,6 +429,7 @@ void carve(dsg_handle* h) {
     }
     for (auto& l : h->lin)
         if (l.lnact) { l.du = take((size_t)groups_of(l.l.K) * 256); l.rs = take(64); }
+    for (auto& a : h->attn) { a.v = take((size_t)groups_of(a.N) * 256); a.dv = take((size_t)groups_of(a.N) * 256); }
     h->tr_yt_frag = take((size_t)groups_of(h->d.input_dim) * 256);
     h->tr_deps = take((size_t)groups_of(h->d.input_dim) * 256);
     h->tr_per_tile = o;
@@ -858,7 +886,78 @@ bool launch_res_lin_h(const dsg_handle* h, const ResP& r, const BlockArgs& b, co
 
 bool split_ctx(const dsg_handle* h, const RunCtx& c) { return h->use_split && c.cond_pre; }
 
+// AttentionBlock: one launch per operator, exact float32 MFMA under both precision modes (dsg_attn.hpp)
+void launch_attn(const dsg_handle* h, const Op& op, const RunCtx& c, hipStream_t s) {
+    const AttnP& t = h->attn[op.p];
+    const float* A = h->arena;
+    const int tpp = cdiv(c.nrows, 32);
+    AttnArgs a;
+    memset(&a, 0, sizeof a);
+    a.l.in = seg_of(h, op.in0);
+    a.l.in_width = t.N; a.l.in_groups = groups_of(t.N); a.l.out_width = t.N;
+    a.l.ntiles = tpp * c.npass; a.l.tiles_per_pass = tpp; a.l.nrows = c.nrows;
+    a.l.inv_in_w = a.l.inv_out_w = 1.0f / (float)t.N;
+    const Seg o = seg_of(h, op.out);
+    a.l.out = const_cast<float*>(o.data); a.l.out_stats = const_cast<float*>(o.stats);
+    a.Wv = A + t.Wvp; a.bv = A + t.bvp; a.Wo = A + t.Wop; a.bo = A + t.bop;
+    a.save_v = c.train ? trp(h, t.v) : nullptr;
+    const dim3 grid(cdiv(a.l.ntiles, kWavesPerBlock)), block(256);
+    if (split_ctx(h, c) && t.N >= 64) {          // dsg_set_precision: the split-f16 form is the default from 64 wide on
+        a.l.range_flag = h->range_flag;
+        a.Wvh = reinterpret_cast<const uint4*>(A + t.Wvh); a.Woh = reinterpret_cast<const uint4*>(A + t.Woh);
+        a.mv = h->maxabs + t.proj.w; a.mo = h->maxabs + t.out.w;
+        if (t.N == 64) hipLaunchKernelGGL(k_attn_h<2>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(k_attn_h<4>, grid, block, 0, s, a);
+        return;
+    }
+    switch (cdiv(t.N, 32)) {
+        case 1: hipLaunchKernelGGL(k_attn<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_attn<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_attn<4>, grid, block, 0, s, a); break;
+    }
+}
+void launch_attn_bwd(const dsg_handle* h, const Op& op, int tiles, hipStream_t s) {
+    const AttnP& t = h->attn[op.p];
+    const float* A = h->arena;
+    AttnBwdArgs a;
+    memset(&a, 0, sizeof a);
+    a.gout_a = trp(h, h->tensors[op.out].ga);
+    a.gout_b = h->tensors[op.out].is_skip ? trp(h, h->tensors[op.out].gb) : nullptr;
+    a.WoT = A + t.WoT; a.WvT = A + t.WvT;
+    a.dv = trp(h, t.dv);
+    // a STORE into the producer's chain slot, as every backward kernel here does (ga has one writer, gb the skip consumer): the residual
+    // block in front of an attention operator is never a skip tensor and the operator is its only consumer (checked in create_impl)
+    a.gin = trp(h, h->tensors[op.in0].ga);
+    a.groups = groups_of(t.N); a.ntiles = tiles;
+    const dim3 grid(cdiv(tiles, kWavesPerBlock)), block(256);
+    switch (cdiv(t.N, 32)) {
+        case 1: hipLaunchKernelGGL(k_attn_bwd<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_attn_bwd<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_attn_bwd<4>, grid, block, 0, s, a); break;
+    }
+}
+
+bool fusable(const dsg_handle* h, const Op& op);
+// Exact path, two-pass launches with the step counter (the reverse loop, dsg_time_op): a narrow operator OUTSIDE the fused run (fuse_lo / fuse_hi is only the longest run: a net with two narrow
+// runs, or one whose run the attention operators cut up, has others) goes through k_fused_narrow as a chain of ONE operator (second
+// half of the table, prepare_fused) -- the register-input form of the block body, which is what the exact path's sampling launches of
+// every shipped net run for <= 32-wide blocks.  The plain per-operator launch (k_resblock<32> with the step counter, precomputed
+// condition embeddings and two passes of >= 2 row tiles each in one launch) returns a wrong UNCONDITIONAL pass (eps off by ~1e-2
+// relative; one tile per pass and the conditional pass are exact) -- with or without attention (proj_dim 32, dims (64, 32):
+// test_attention_gpu.test_exact_path_sampling_of_a_net_with_two_narrow_runs).  The cause is not found; no launch takes that path any more.
+bool narrow_singles(const dsg_handle* h, const RunCtx& c) {
+    return !split_ctx(h, c) && !c.train && c.step_ptr && !c.ts;
+}
+
 void launch_op(const dsg_handle* h, const Op& op, const RunCtx& c, hipStream_t s) {
+    if (op.kind == OP_ATTN) { launch_attn(h, op, c, s); return; }
+    const long long opi = &op - h->ops.data();       // every caller passes an element of h->ops; anything else takes the plain launch below
+    if (narrow_singles(h, c) && fusable(h, op) && opi >= 0 && opi < (long long)h->ops.size()) {
+        const int ntiles = cdiv(c.nrows, 32) * c.npass;
+        const size_t at = h->ops.size() + 1 + (size_t)opi;
+        hipLaunchKernelGGL(k_fused_narrow, dim3(cdiv(ntiles, kWavesPerBlock)), dim3(256), 0, s, (const FusedOp*)(h->fused_dev + at), 1, ntiles);
+        return;
+    }
     if (op.kind == OP_RES) {
         BlockArgs a;
         fill_block_args(h, op, c, a);
@@ -889,7 +988,8 @@ bool fusable(const dsg_handle* h, const Op& op) {
 // Upload the operator descriptors of the fused narrow run for this context (stream ordered; replayed graphs read them).
 int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
     const int n = h->fuse_hi - h->fuse_lo;
-    if (n < 2) return 0;
+    const bool singles = narrow_singles(h, c);
+    if (n < 2 && !singles) return 0;
     const bool sp = split_ctx(h, c);
     if (c.train) {
         // training forward: split path only; the table depends on the workspaces and the batch, not on the step -> cached
@@ -916,6 +1016,21 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
     }
     HIPCK(hipStreamSynchronize(s));  // the host tables may still be the source of an earlier async copy
     if (sp) h->fusedh_host.resize(n); else h->fused_host.resize(n);
+    if (singles) {
+        const size_t nops = h->ops.size();
+        h->fused_host.assign(2 * (nops + 1), FusedOp{});
+        for (size_t k = 0; k < nops; ++k) {
+            const Op& op = h->ops[k];
+            if (!fusable(h, op)) continue;
+            FusedOp& f = h->fused_host[nops + 1 + k];
+            memset(&f, 0, sizeof f);
+            f.kind = op.kind == OP_RES ? 0 : 1;
+            f.N = f.kind == 0 ? h->res[op.p].N : h->lin[op.p].l.N;
+            f.sclin = f.kind == 0 ? (int)h->res[op.p].sclin : 0;
+            if (f.kind == 0) fill_block_args(h, op, c, f.b); else fill_lin_args(h, op, c, f.l);
+            f.pad = 2 | 1;             // a chain of one: input into registers, output stored
+        }
+    }
     for (int i = 0; i < n; ++i) {
         const Op& op = h->ops[h->fuse_lo + i];
         BlockArgs b; LinArgs l;
@@ -957,7 +1072,7 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
         }
     }
     if (sp) HIPCK(hipMemcpyAsync(c.train ? h->fusedh_train_dev : h->fusedh_dev, h->fusedh_host.data(), h->fusedh_host.size() * sizeof(FusedOpH), hipMemcpyHostToDevice, s));
-    else HIPCK(hipMemcpyAsync(h->fused_dev, h->fused_host.data(), n * sizeof(FusedOp), hipMemcpyHostToDevice, s));
+    else HIPCK(hipMemcpyAsync(h->fused_dev, h->fused_host.data(), (singles ? h->fused_host.size() : (size_t)n) * sizeof(FusedOp), hipMemcpyHostToDevice, s));
     if (sp && !c.train) {
         // the whole net's table for k_unet_tile: the run's entries as above, every other operator stored (its consumer reads memory)
         const int nops = (int)h->ops.size();
@@ -970,6 +1085,7 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
             memset(&f, 0, sizeof f);
             if (i >= h->fuse_lo && i < h->fuse_hi) { f = h->fusedh_host[i - h->fuse_lo]; continue; }
             f.store_out = 1;
+            if (op.kind == OP_ATTN) { ok = false; break; }      // k_unet_tile has not learned the operator: per-operator launches
             if (op.kind == OP_RES) {
                 const ResP& r = h->res[op.p];
                 BlockArgs b;
@@ -1379,6 +1495,9 @@ int ensure_train_workspace(dsg_handle* h, int rows, int T) {
     HIPCK(hipMalloc(&h->tr_ws, tiles * h->tr_per_tile * sizeof(float)));
     HIPCK(hipMemset(h->tr_ws, 0, tiles * h->tr_per_tile * sizeof(float)));
     HIPCK(hipMalloc(&h->tr_slabs, (size_t)max_chunks * h->slab_stride * sizeof(float)));
+    // INVARIANT (AttentionBlock): the slab entries of attn.norm.* and of rows 0:2d of attn.projection.* are written by NOTHING after this
+    // memset -- no weight-gradient unit, column sum or one-hot unit has an out_off inside them -- so the fixed-order reduce stores exact
+    // zeros for them into the caller's bucket on every step.  Whoever adds a writer to those ranges must zero them per step instead.
     HIPCK(hipMemset(h->tr_slabs, 0, (size_t)max_chunks * h->slab_stride * sizeof(float)));
     HIPCK(hipMalloc(&h->tr_gsum, h->slab_stride * sizeof(float)));
     // + one set per early weight-gradient part + the complete set of the step's tail (the blocks' slots AND the Linears')
@@ -1554,6 +1673,19 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
 
     for (const Op& op : h->ops) {
         ++cur_op;
+        if (op.kind == OP_ATTN) {
+            // two plain Linears as far as the weight gradients go: output (G = dy, A = v) and rows 2d:3d of projection (G = dv, A = x).
+            // Nothing writes the slab entries of projection's q / k rows and of attn.norm: the fixed-order reduce stores their zeros
+            // into the caller's bucket every step.
+            const AttnP& t = h->attn[op.p];
+            const float *ga = grad_a(op.out), *gb = grad_b(op.out), *dv = trp(h, t.dv);
+            const long long d = t.N;
+            wgrad(ga, gb, t.N, A_RAW, gseg(trp(h, t.v), t.N), none(), nullptr, nullptr, nullptr, P[t.out.w].off, t.N);
+            colsum(ga, gb, groups_of(t.N), none(), none(), nullptr, t.N, 0, P[t.out.b].off, -1, -1);
+            wgrad(dv, nullptr, t.N, A_RAW, seg_of(h, op.in0), none(), nullptr, nullptr, nullptr, P[t.proj.w].off + 2 * d * d, t.N);
+            colsum(dv, nullptr, groups_of(t.N), none(), none(), nullptr, t.N, 0, P[t.proj.b].off + 2 * d, -1, -1);
+            continue;
+        }
         if (op.kind == OP_RES) {
             const ResP& r = h->res[op.p];
             const Seg in0 = seg_of(h, op.in0), in1 = op.in1 >= 0 ? seg_of(h, op.in1) : none();
@@ -1754,7 +1886,7 @@ const char* dsg_build_id(void) {
     return id + 13;
 }
 
-dsg_handle* dsg_create(const dsg_unet_desc* desc) {
+static dsg_handle* create_impl(const dsg_unet_desc* desc, const int* is_attn, int middle_attn) {
     if (!desc) { fail("null desc"); return nullptr; }
     const dsg_unet_desc d = *desc;
     if (d.n_res < 1 || d.n_res > 8 || d.n_blocks < 1 || d.input_dim < 1 || d.cond_dim < 1) {
@@ -1766,6 +1898,21 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
     }
     for (int i = 0; i < d.n_res; ++i)
         if (!width_supported(d.dims[i])) { fail("dims[%d]=%d unsupported (4, 8, 16, 32, 64, 128)", i, d.dims[i]); return nullptr; }
+    // is_attn[i] of the blocks of resolution i; the extra blocks at the last width (down path) and at proj_dim (up path) use the
+    // loop's final i, as the reference constructor does (UNetCF.py:289,310)
+    auto attn_at = [&](int i) { return is_attn && is_attn[i] != 0; };
+    {
+        std::vector<int> aw;      // every width an AttentionBlock is asked for
+        for (int i = 0; i < d.n_res; ++i) {
+            if (!attn_at(i)) continue;
+            aw.push_back(i > 0 ? d.dims[i - 1] : d.proj_dim);      // down blocks of resolution i
+            aw.push_back(d.dims[i]);                               // up blocks of resolution i (and the extra down blocks of the last one)
+            if (i == 0) aw.push_back(d.proj_dim);                  // the extra up blocks
+        }
+        if (middle_attn) aw.push_back(d.dims[d.n_res - 1]);
+        for (int w4 : aw)
+            if (w4 < 8 || !width_supported(w4)) { fail("AttentionBlock width %d unsupported (8, 16, 32, 64, 128)", w4); return nullptr; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fail("no HIP device: libdiffsg_hip needs an MI355X"); return nullptr; }
 
@@ -1788,15 +1935,26 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
     skips.push_back(cur);
     int w = d.proj_dim, idx = 0;
     char nm[64];
-    auto push_down_res = [&](int width) {
+    // res, then attn (UNetCF.py:177-178): the operator sits behind its residual block with an output tensor of its own; what the block
+    // hands on -- and what the down path pushes as the skip -- is the attention output
+    auto push_attn = [&](const char* prefix, int width, bool is_skip) {
+        snprintf(nm, sizeof nm, "%s.attn", prefix);
+        const int p = add_attn(h, nm, width);
+        const int out = add_tensor(h, width, is_skip);
+        h->ops.push_back(Op{OP_ATTN, p, cur, -1, out, nm});
+        cur = out;
+    };
+    auto push_down_res = [&](int width, bool attn) {
         snprintf(nm, sizeof nm, "down.%d.res", idx);
         const int p = add_res(h, nm, width, 0, width);
-        const int out = add_tensor(h, width, true);
+        const int out = add_tensor(h, width, !attn);
         h->ops.push_back(Op{OP_RES, p, cur, -1, out, nm});
-        cur = out; skips.push_back(cur); ++idx;
+        cur = out;
+        if (attn) { char pf[32]; snprintf(pf, sizeof pf, "down.%d", idx); push_attn(pf, width, true); }
+        skips.push_back(cur); ++idx;
     };
     for (int i = 0; i < d.n_res; ++i) {
-        for (int b = 0; b < d.n_blocks; ++b) push_down_res(w);
+        for (int b = 0; b < d.n_blocks; ++b) push_down_res(w, attn_at(i));
         snprintf(nm, sizeof nm, "down.%d.lin", idx);
         LinOpP l; l.l = add_linear(h, nm, w, d.dims[i]);
         h->lin.push_back(l);
@@ -1806,7 +1964,7 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
         cur = out; skips.push_back(cur); ++idx;
         w = d.dims[i];
         if (i == d.n_res - 1)
-            for (int b = 0; b < d.n_blocks; ++b) push_down_res(w);
+            for (int b = 0; b < d.n_blocks; ++b) push_down_res(w, attn_at(i));
     }
     for (int m = 1; m <= 2; ++m) {
         snprintf(nm, sizeof nm, "middle.res%d", m);
@@ -1814,18 +1972,21 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
         const int out = add_tensor(h, w, false);
         h->ops.push_back(Op{OP_RES, p, cur, -1, out, nm});
         cur = out;
+        if (m == 1 && middle_attn) push_attn("middle", w, false);
     }
     idx = 0;
-    auto push_up_res = [&](int width) {
+    auto push_up_res = [&](int width, bool attn) {
         snprintf(nm, sizeof nm, "up.%d.res", idx);
         const int sk = skips.back(); skips.pop_back();
         const int p = add_res(h, nm, width, h->tensors[sk].width, width);
         const int out = add_tensor(h, width, false);
         h->ops.push_back(Op{OP_RES, p, cur, sk, out, nm});
-        cur = out; ++idx;
+        cur = out;
+        if (attn) { char pf[32]; snprintf(pf, sizeof pf, "up.%d", idx); push_attn(pf, width, false); }
+        ++idx;
     };
     for (int i = d.n_res - 1; i >= 0; --i) {
-        for (int b = 0; b < d.n_blocks + 1; ++b) push_up_res(w);
+        for (int b = 0; b < d.n_blocks + 1; ++b) push_up_res(w, attn_at(i));
         const int nw = i > 0 ? d.dims[i - 1] : d.proj_dim;
         snprintf(nm, sizeof nm, "up.%d.lin", idx);
         LinOpP l; l.l = add_linear(h, nm, w, nw);
@@ -1836,7 +1997,7 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
         cur = out; ++idx;
         w = nw;
         if (i == 0)
-            for (int b = 0; b < d.n_blocks + 1; ++b) push_up_res(w);
+            for (int b = 0; b < d.n_blocks + 1; ++b) push_up_res(w, attn_at(i));
     }
     {
         LinOpP f;
@@ -1848,6 +2009,12 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
     }
     for (const ResP& r : h->res)
         if ((r.in1 && r.in1 != r.in0) || (r.sclin != (r.in1 != 0))) { fail("internal: unexpected block shape"); delete h; return nullptr; }
+    for (size_t i = 0; i < h->ops.size(); ++i) {     // an attention operator is the ONLY reader of its input (k_attn_bwd stores into its `ga`)
+        if (h->ops[i].kind != OP_ATTN) continue;
+        int readers = 0;
+        for (const Op& o : h->ops) readers += (o.in0 == h->ops[i].in0) + (o.in1 == h->ops[i].in0);
+        if (readers != 1 || h->tensors[h->ops[i].in0].is_skip) { fail("internal: attention input with another reader"); delete h; return nullptr; }
+    }
     carve(h);
     {   // longest consecutive run of narrow operators
         int best_lo = 0, best_hi = 0, lo = -1;
@@ -1877,7 +2044,7 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
               hipMalloc(&h->fusedh_dev, (h->ops.size() + 1) * sizeof(FusedOpH)) == hipSuccess &&
               hipMalloc(&h->tileops_dev, (h->ops.size() + 1) * sizeof(FusedOpH)) == hipSuccess &&
               hipMalloc(&h->maxabs, (h->params.size() + 1) * sizeof(float)) == hipSuccess &&
-              hipMalloc(&h->fused_dev, (h->ops.size() + 1) * sizeof(FusedOp)) == hipSuccess &&
+              hipMalloc(&h->fused_dev, 2 * (h->ops.size() + 1) * sizeof(FusedOp)) == hipSuccess &&
               hipMalloc(&h->arena, h->arena_floats * sizeof(float)) == hipSuccess &&
               hipMemset(h->arena, 0, h->arena_floats * sizeof(float)) == hipSuccess &&
               hipMalloc(&h->tdesc_dev, h->res.size() * sizeof(TimeBlockDesc)) == hipSuccess &&
@@ -1906,6 +2073,13 @@ dsg_handle* dsg_create(const dsg_unet_desc* desc) {
     }
     if (!ok) { fail("device allocation failed in dsg_create"); dsg_destroy(h); return nullptr; }
     return h;
+}
+
+dsg_handle* dsg_create(const dsg_unet_desc* desc) { return create_impl(desc, nullptr, 0); }
+
+dsg_handle* dsg_create_attn(const dsg_unet_desc* desc, const int* is_attn, int middle_attn) {
+    if (desc && !is_attn && desc->n_res > 0) { fail("dsg_create_attn: null is_attn"); return nullptr; }
+    return create_impl(desc, is_attn, middle_attn);
 }
 
 void dsg_destroy(dsg_handle* h) {
@@ -2040,6 +2214,17 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
                 padv(P[l.ln.b].ptr, nullptr, l.l.K, 0, l.betap, KG * 8 + 32);
             }
         }
+        for (const AttnP& t : h->attn) {
+            const int NT = cdiv(t.N, 32), NG = groups_of(t.N);
+            const long long d = t.N, tot = (long long)NT * NG * 256;
+            const float* Wv = P[t.proj.w].ptr + 2 * d * d;
+            push(0, Wv, nullptr, t.Wvp, t.N, t.N, t.N, 0, NT, tot);
+            push(1, Wv, nullptr, t.WvT, t.N, t.N, t.N, 0, NT, tot);
+            padv(P[t.proj.b].ptr + 2 * d, nullptr, t.N, 0, t.bvp, NT * 32);
+            pack(t.out, t.N, 0, t.Wop);
+            packT(t.out, t.N, 0, t.WoT);
+            padv(P[t.out.b].ptr, nullptr, t.N, 0, t.bop, NT * 32);
+        }
         {   // fp16-split planes of the wide blocks
             std::vector<const float*> mp; std::vector<long long> mn; std::vector<PackHDesc> hd;
             h->mx_param.clear();
@@ -2081,6 +2266,16 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
                 else pushhT(r.l3, nullptr, 0, r.N, 0, r.W3Th);
             }
             for (const LinOpP& l : h->lin) { want(l.l); pushh(l.l, nullptr, 0, l.l.K, 0, l.Wh); }
+            for (const AttnP& t : h->attn) {
+                if (t.N < 64) continue;
+                // Wv = rows 2d:3d of projection.weight, scaled by max| | of the WHOLE tensor (the word k_attn_h reads): one [d][d] matrix
+                want(t.proj); want(t.out);
+                LinearP lo = t.out;
+                pushh(lo, nullptr, 0, t.N, 0, t.Woh);
+                pushh(lo, nullptr, 0, t.N, 0, t.Wvh);
+                PackHDesc& dv = hd.back();
+                dv.W = P[t.proj.w].ptr + 2 * (size_t)t.N * t.N; dv.m_self = h->maxabs + t.proj.w;
+            }
             h->mx_n = (int)mp.size(); h->packh_n = (int)hd.size(); h->packh_blocks = hb;
             if (h->mx_n) {
                 if (!h->mx_ptrs_dev) {
@@ -2604,6 +2799,7 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     for (int oi = (int)h->ops.size() - 1; oi >= 0; --oi) {
         const Op& op = h->ops[oi];
         if (op.kind == OP_PROJ) continue;
+        if (op.kind == OP_ATTN) { launch_attn_bwd(h, op, tiles, s); continue; }
         if (h->use_split && h->fbwd_n > 0 && oi == h->fuse_hi - 1) {
             // the narrow run: one launch walks its operators in reverse (k_fused_narrow_bwd_h)
             hipLaunchKernelGGL(k_fused_narrow_bwd_h, dim3(cdiv(tiles, kWavesPerBlock)), dim3(256), 0, s, h->fbwd_dev, h->fbwd_n, tiles);
@@ -2966,6 +3162,10 @@ int dsg_op_info(const dsg_handle* h, int op, char* name, double* flops_per_row, 
         macs2 = (double)in * r.N + 2.0 * r.N * r.N + (r.sclin ? (double)in * r.N : 0.0);
         macs_cond = (double)h->d.cond_dim * r.N;
         bytes = 2.0 * 4.0 * (in + r.N);
+    } else if (o.kind == OP_ATTN) {
+        const double d = h->attn[o.p].N;
+        macs2 = 2.0 * d * d;
+        bytes = 2.0 * 4.0 * (d + d);
     } else {
         const LinOpP& l = h->lin[o.p];
         macs2 = (double)l.l.K * l.l.N;
@@ -2986,6 +3186,7 @@ int dsg_time_op(dsg_handle* h, int op, int B, int iters, float* ms_avg, void* st
     const int zero = 0;
     HIPCK(hipMemcpyAsync(h->step_dev, &zero, sizeof(int), hipMemcpyHostToDevice, s));
     RunCtx c{B, 2, cdiv(B, 32), h->ywork, h->eps, h->step_dev, nullptr, false, true};
+    if (narrow_singles(h, c) && prepare_fused(h, c, s)) return 1;     // exact path: the single-operator table of this context
     hipEvent_t e0, e1;
     HIPCK(hipEventCreate(&e0));
     HIPCK(hipEventCreate(&e1));

@@ -20,8 +20,9 @@ extern "C" {
 
 typedef struct dsg_handle dsg_handle;
 
-/* UNet1D constructor arguments (ddpm_opt/UNetCF.py:262-266); is_attn / middle_attn are always False in the
- * reference's call sites (classifier_free_MSR.py:202-203, _CO.py:218-219, _NU.py:230-231) and are not supported. */
+/* UNet1D constructor arguments (ddpm_opt/UNetCF.py:262-266) without the attention flags: is_attn / middle_attn are always
+ * False in the reference's call sites (classifier_free_MSR.py:202-203, _CO.py:218-219, _NU.py:230-231), and this layout is what
+ * existing callers hold.  A net with AttentionBlocks is created with dsg_create_attn, which takes the flags beside it. */
 typedef struct {
     int input_dim;
     int proj_dim;
@@ -32,6 +33,12 @@ typedef struct {
 } dsg_unet_desc;
 
 dsg_handle* dsg_create(const dsg_unet_desc* desc);
+/* The same with UNet1D's is_attn[n_res] (non-zero = the Down/UpBlocks of that resolution run `res` then `attn`, UNetCF.py:160-203,
+ * 278-311) and middle_attn (MiddleBlock: res1, attn, res2).  AttentionBlock(d) has n_heads = 1, d_k = d and sees a sequence of
+ * length 1: its softmax is identically 1, so it computes out = output(Wv x + bv) + x with Wv / bv = rows 2d:3d of `projection`;
+ * its parameters (`norm`, `projection`, `output`) appear in the parameter table in state-dict order, the gradients of `norm` and
+ * of projection's q / k rows are exact zeros.  Widths 8 .. 128.  dsg_create(desc) == dsg_create_attn(desc, zeros, 0). */
+dsg_handle* dsg_create_attn(const dsg_unet_desc* desc, const int* is_attn /* n_res */, int middle_attn);
 void dsg_destroy(dsg_handle* h);
 const char* dsg_last_error(void);
 /* sha256 of the sources this binary was built from (diffsg_amd/_lib.py refuses to load a library whose id differs from
