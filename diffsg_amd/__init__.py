@@ -6,5 +6,6 @@ Host-side mirror of the reference's Python object API (ddpm_opt/*.py) over the C
 from .UNetCF import UNet1D  # noqa: F401
 from .diffusion import generate_cosine_schedule, init_weights  # noqa: F401
 from .ema import ExponentialMovingAverage  # noqa: F401
+from .repeated import BestOf, best_of  # noqa: F401
 
-__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage"]
+__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of"]

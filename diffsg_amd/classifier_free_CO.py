@@ -35,6 +35,9 @@ class DDPM(DDPMCore):
         from .decode import co_decode
         return co_decode(y)
 
+    def _best_of_problem(self):
+        return "co", {}
+
 
 def data_preprocess_co(X):
     """utils/dataset.py:26-51: (6 per-node + 7 common raw features) -> 3 cost features per node
@@ -121,8 +124,9 @@ def customized_real_decoder(Y_pred):
 
 
 @torch.no_grad()
-def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print):
-    """classifier_free_CO.py:293-356."""
+def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print, repeats=1):
+    """classifier_free_CO.py:293-356.  `repeats` > 1: that many draws per test row, the one with the lowest cost scored
+    (DDPM.sample_best); 1 is the reference's single draw."""
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     device = _device()
@@ -130,16 +134,21 @@ def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, bat
     diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
     diffusion_model.to(device)
     X = torch.tensor(X_test, dtype=torch.float32)
-    # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
-    # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-    if batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
-    else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
-    Yd = customized_real_decoder(Y_pred)
-    pred_cost, true_cost = cost_calc(Xt, Yd), cost_calc(Xt, Yt)
+    if repeats > 1:
+        best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size)
+        Yd, pred_cost = best.solution, best.objective
+    else:
+        # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
+        # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
+        if batch_size % 32 == 0:
+            Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
+        else:
+            Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
+        Yd = customized_real_decoder(Y_pred)
+        pred_cost = cost_calc(Xt, Yd)
+    true_cost = cost_calc(Xt, Yt)
     weights = 2 ** torch.arange(node_num - 1, -1, -1, device=device)
     pred_cls = ((Yd > 0.1).long() * weights).sum(dim=1)
     true_cls = ((Yt > 0.1).long() * weights).sum(dim=1)
@@ -147,6 +156,8 @@ def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, bat
     out = {"exceeded_ratio": float(torch.sum(pred_cost) / torch.sum(true_cost)),
            "avg_cost_diff": float(torch.mean(pred_cost - true_cost)),
            "terrible": int(terrible), "accuracy": int((pred_cls == true_cls).sum()), "n": int(X.shape[0])}
+    if repeats > 1:
+        out["repeats"] = int(repeats)
     log(f"exceeded ratio: {out['exceeded_ratio']}")
     log(f"avg cost diff:\n {out['avg_cost_diff']}")
     log(f"terrible samples num: {out['terrible']}/{out['n']}.")

@@ -37,6 +37,9 @@ class DDPM(DDPMCore):
         from .decode import row_softmax
         return row_softmax(y) if i <= 2 else msr_decode(y)
 
+    def _best_of_problem(self):
+        return "msr", {"W": self.W}
+
 
 def msr_data_load(dataset_path):
     """classifier_free_MSR.py:159-184.  CSV columns: M gains | 1 rate | M powers.  W comes from the FILE NAME
@@ -95,8 +98,9 @@ def custom_decoder(Y_pred):
 
 
 @torch.no_grad()
-def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print):
-    """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well."""
+def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print, repeats=1):
+    """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats` > 1: that many draws per test
+    row, the one with the best sum rate scored (DDPM.sample_best); 1 is the reference's single draw."""
     _, _, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
@@ -104,6 +108,17 @@ def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batc
     diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
     diffusion_model.to(device)
     X = torch.tensor(X_test, dtype=torch.float32)
+    if repeats > 1:
+        Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
+        Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
+        from .decode import msr_rate
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size).objective
+        true_rate = msr_rate(Yt, Xt)
+        out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
+               "avg_rate_diff": float(torch.mean(pred_rate - true_rate)), "repeats": int(repeats)}
+        log(f"less ratio: {out['less_ratio']}")
+        log(f"avg rate diff:\n {out['avg_rate_diff']}")
+        return out
     # each 512-row chunk is its own sample() call, as in the reference (:273-279): the early-step renorm is per call
     # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
     # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls

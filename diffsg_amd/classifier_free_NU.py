@@ -36,6 +36,10 @@ class DDPM(DDPMCore):
         cc = self.custom_config or {}
         return nu_decode(y, cc.get("width", 400), cc.get("height", 400), self.P_sum)
 
+    def _best_of_problem(self):
+        cc = self.custom_config or {}
+        return "nu", {"width": cc.get("width", 400), "height": cc.get("height", 400), "p_sum": self.P_sum}
+
 
 def nu_data_load(dataset_path, width, height):
     """classifier_free_NU.py:184-210.  CSV columns: 2K user coords | 2 UAV coords | K powers | 1 rate.  P_sum comes
@@ -103,8 +107,9 @@ def rate_calc(Y_pred_decoded, X):
 
 @torch.no_grad()
 def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, width=400, height=400,
-                 log=print):
-    """classifier_free_NU.py:306-361."""
+                 log=print, repeats=1):
+    """classifier_free_NU.py:306-361.  `repeats` > 1: that many draws per test row, the one with the best rate scored
+    (DDPM.sample_best); 1 is the reference's single draw."""
     _, _, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
     device = _device()
@@ -114,21 +119,29 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
     X = torch.tensor(X_test, dtype=torch.float32)
     # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
     # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-    if batch_size % 32 == 0:
+    if repeats > 1:
+        Y_pred = None                       # sampled below, `repeats` rounds of the same calls
+    elif batch_size % 32 == 0:
         Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
     else:
         Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
     Xt = X.to(device).clone()
     Xt[:, 0::2] *= width
     Xt[:, 1::2] *= height
-    Yd = custom_decoder(Y_pred, width, height, P_sum)
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
     Yt[:, 0] *= width
     Yt[:, 1] *= height
     Yt[:, 2:] *= P_sum
-    pred_rate, true_rate = rate_calc(Yd, Xt), rate_calc(Yt, Xt)
+    if repeats > 1:
+        # width / height of THIS call, as custom_decoder below gets them (the hook reads the model's custom_config: the same values)
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size).objective
+    else:
+        pred_rate = rate_calc(custom_decoder(Y_pred, width, height, P_sum), Xt)
+    true_rate = rate_calc(Yt, Xt)
     out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
            "avg_rate_diff": float(torch.mean(pred_rate - true_rate))}
+    if repeats > 1:
+        out["repeats"] = int(repeats)
     log(f"less ratio: {out['less_ratio']}")
     log(f"avg rate diff:\n {out['avg_rate_diff']}")
     return out

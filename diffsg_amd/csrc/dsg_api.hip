@@ -11,6 +11,7 @@
 #include "dsg_attn.hpp"
 #include "dsg_train_split.hpp"
 #include "dsg_eval.hpp"
+#include "dsg_best.hpp"
 #include "dsg_labelgen.hpp"
 #include "dsg_cogen.hpp"
 #include "dsg_nugen.hpp"
@@ -3061,6 +3062,54 @@ int dsg_nu_rate(const float* Yd, const float* X, float* rate, long long rows, in
     if (K > kNuMaxUsers) return fail("dsg_nu_rate: K = %d users (at most %d)", K, kNuMaxUsers);
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_nu_rate, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Yd, X, rate, rows, K);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// Best of n rounds per condition (dsg_best.hpp): one statistics pass (MSR / NU), one selection launch.
+int dsg_best_of(int problem, const float* Y, const float* X, int n, long long B, int D, const float* params, float* solution,
+                float* objective, int* round, float* objectives, int accumulate, int round0, void* stream) {
+    if (problem < DSG_PROBLEM_MSR || problem > DSG_PROBLEM_NU) return fail("dsg_best_of: problem = %d (DSG_PROBLEM_MSR / _CO / _NU)", problem);
+    if (B < 0 || D < 1 || n < 0 || round0 < 0 || (problem != DSG_PROBLEM_CO && !params)) return fail("dsg_best_of: bad arguments");
+    if ((long long)n * B > 2147483647LL) return fail("dsg_best_of: n * B = %lld candidate rows (at most 2^31 - 1)", (long long)n * B);
+    if (problem == DSG_PROBLEM_NU && D < 3) return fail("dsg_best_of: NU with D = %d (two position columns and at least one power column)", D);
+    if (problem == DSG_PROBLEM_NU && D - 2 > kNuMaxUsers) return fail("dsg_best_of: NU with K = %d users (at most %d)", D - 2, kNuMaxUsers);
+    if (problem == DSG_PROBLEM_MSR && D > 64 * kSoftEpl) return fail("dsg_best_of: MSR rows of D = %d (at most %d)", D, 64 * kSoftEpl);
+    if (problem == DSG_PROBLEM_CO && D > kSoftEpl) return fail("dsg_best_of: CO rows of D = %d nodes (at most %d)", D, kSoftEpl);
+    if (B == 0 || n == 0) return 0;
+    if (eval_args(Y, X, B, D, "dsg_best_of") || !solution || !objective || !round) return fail("dsg_best_of: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    float2* scratch = nullptr;                        // [n] per-round (min, max), then the partials [n][nparts]
+    if (problem != DSG_PROBLEM_CO) {
+        const int c0 = 0, c1 = problem == DSG_PROBLEM_MSR ? D : 2;
+        const int w = c1 - c0, lpr = w >= 64 ? 64 : (w >= 16 ? 16 : (w >= 4 ? 4 : 1));
+        const long long want = (B + 4LL * (64 / lpr) - 1) / (4LL * (64 / lpr));
+        const int nparts = (int)(want < kEvalParts ? want : kEvalParts);
+        HIPCK(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)n * (1 + nparts) * sizeof(float2), s));
+        const unsigned gy = (unsigned)(n < 65535 ? n : 65535);
+        hipLaunchKernelGGL(k_best_minmax_partial, dim3(nparts, gy), dim3(256), 0, s, Y, n, B, D, c0, c1, scratch + n);
+        hipLaunchKernelGGL(k_best_minmax_final, dim3(gy), dim3(256), 0, s, scratch + n, n, nparts, scratch);
+    }
+    auto grid = [&](int lpr) { const long long rpb = 4LL * (64 / lpr); return dim3((unsigned)((B + rpb - 1) / rpb)); };
+#define DSG_BEST_MSR(L, Q) hipLaunchKernelGGL((k_best_msr<L, Q>), grid(L), dim3(256), 0, s, Y, X, n, B, D, params[0], scratch, solution, \
+                                              objective, round, objectives, accumulate, round0)
+    if (problem == DSG_PROBLEM_MSR) {
+        // lanes per row = k_row_softmax's for this D; Q = k_msr_rate's lanes per row over that (see k_best_msr)
+        if (D <= 8) DSG_BEST_MSR(1, 1);
+        else if (D <= kSoftEpl) DSG_BEST_MSR(1, 16);
+        else if (D <= 4 * kSoftEpl) DSG_BEST_MSR(4, 4);
+        else if (D <= 160) DSG_BEST_MSR(16, 1);
+        else if (D <= 16 * kSoftEpl) DSG_BEST_MSR(16, 4);
+        else DSG_BEST_MSR(64, 1);
+    } else if (problem == DSG_PROBLEM_CO) {
+        hipLaunchKernelGGL(k_best_co, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, Y, X, n, B, D, solution, objective, round, objectives,
+                           accumulate, round0);
+    } else {
+        hipLaunchKernelGGL(k_best_nu, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, Y, X, n, B, D, params[0], params[1], params[2], scratch,
+                           solution, objective, round, objectives, accumulate, round0);
+    }
+#undef DSG_BEST_MSR
+    if (scratch) HIPCK(hipFreeAsync(scratch, s));
     HIPCK(hipGetLastError());
     return 0;
 }

@@ -81,17 +81,11 @@ __device__ __forceinline__ float group_sum(float v) {
     for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// The row body: the LPR lanes of a row load it (column sub + k * LPR in slot k), leave exp(f(y) - max) in v[] and return the row's
+// sum; `dead` is MODE 2's rule.  Shared with dsg_best.hpp, whose per-round values must be these bit for bit.
 template <int MODE, int LPR>
-__global__ __launch_bounds__(256) void k_row_softmax(const float* __restrict__ y, float* __restrict__ out, long long rows, int D,
-                                                     const float2* __restrict__ part) {
-    constexpr int RPW = 64 / LPR;                       // rows per wave
-    const int lane = threadIdx.x & 63, sub = lane % LPR;
-    const long long r = (blockIdx.x * 4LL + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    const bool live = r < rows;
-    float lo = 0.f, span = 1.f;
-    if (MODE == 1) { const float2 mm = part[0]; lo = mm.x; span = mm.y - mm.x; }
-    const float* yr = y + (live ? r : 0) * D;
-    float v[kSoftEpl];
+__device__ __forceinline__ float softmax_row_regs(const float* __restrict__ yr, int sub, int D, float lo, float span,
+                                                  float (&v)[kSoftEpl], bool& dead) {
     float m = -INFINITY, ymax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < kSoftEpl; ++k) {
@@ -112,7 +106,21 @@ __global__ __launch_bounds__(256) void k_row_softmax(const float* __restrict__ y
         s += v[k];
     }
     s = group_sum<LPR>(s);
-    const bool dead = MODE == 2 && group_max<LPR>(ymax) < -10.0f;
+    dead = MODE == 2 && group_max<LPR>(ymax) < -10.0f;
+    return s;
+}
+template <int MODE, int LPR>
+__global__ __launch_bounds__(256) void k_row_softmax(const float* __restrict__ y, float* __restrict__ out, long long rows, int D,
+                                                     const float2* __restrict__ part) {
+    constexpr int RPW = 64 / LPR;                       // rows per wave
+    const int lane = threadIdx.x & 63, sub = lane % LPR;
+    const long long r = (blockIdx.x * 4LL + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    const bool live = r < rows;
+    float lo = 0.f, span = 1.f;
+    if (MODE == 1) { const float2 mm = part[0]; lo = mm.x; span = mm.y - mm.x; }
+    float v[kSoftEpl];
+    bool dead;
+    const float s = softmax_row_regs<MODE, LPR>(y + (live ? r : 0) * D, sub, D, lo, span, v, dead);
     if (live) {
 #pragma unroll
         for (int k = 0; k < kSoftEpl; ++k) {
@@ -152,6 +160,7 @@ __global__ __launch_bounds__(256) void k_row_softmax_wide(const float* __restric
 }
 
 // MSR objective: rate[r] = sum_c log2(1 + p[r][c] * g[r][c])   (MSR.py:287-288)
+__device__ __forceinline__ float msr_term(float p, float g) { return log2f(1.0f + p * g); }
 template <int LPR>
 __global__ __launch_bounds__(256) void k_msr_rate(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ out,
                                                   long long rows, int D) {
@@ -161,19 +170,14 @@ __global__ __launch_bounds__(256) void k_msr_rate(const float* __restrict__ p, c
     const bool live = r < rows;
     const long long base = (live ? r : 0) * D;
     float s = 0.f;
-    for (int c = sub; c < D; c += LPR) s += log2f(1.0f + p[base + c] * g[base + c]);
+    for (int c = sub; c < D; c += LPR) s += msr_term(p[base + c], g[base + c]);
     s = group_sum<LPR>(s);
     if (live && sub == 0) out[r] = s;
 }
 
 // CO objective (CO.py:255-278): nodes with Y > 0.1 are offloaded and share the unallocated remainder equally;
 // cost = sum_nodes (1-D)*local + D*(transition + exec / share).  X row = [local, transition, exec] per node.
-__global__ __launch_bounds__(256) void k_co_cost(const float* __restrict__ X, const float* __restrict__ Y, float* __restrict__ out,
-                                                 long long rows, int n) {
-    const long long r = blockIdx.x * 256LL + threadIdx.x;
-    if (r >= rows) return;
-    const float* y = Y + r * n;
-    const float* x = X + r * 3 * n;
+__device__ __forceinline__ float co_cost_row(const float* __restrict__ x, const float* __restrict__ y, int n) {
     float ysum = 0.f;
     int dsum = 0;
     for (int i = 0; i < n; ++i)
@@ -186,37 +190,40 @@ __global__ __launch_bounds__(256) void k_co_cost(const float* __restrict__ X, co
         const float share = y[i] + spread;
         cost += off ? x[3 * i + 1] + x[3 * i + 2] / share : x[3 * i];   // (1 - D) * local + D * (trans + exec / share), D in {0, 1}
     }
-    out[r] = cost;
+    return cost;
+}
+__global__ __launch_bounds__(256) void k_co_cost(const float* __restrict__ X, const float* __restrict__ Y, float* __restrict__ out,
+                                                 long long rows, int n) {
+    const long long r = blockIdx.x * 256LL + threadIdx.x;
+    if (r >= rows) return;
+    out[r] = co_cost_row(X + r * 3 * n, Y + r * n, n);
 }
 
 // NU decoder (NU.py:267-276): columns 0, 1 = UAV position, min-max scaled with the GLOBAL (lo, hi) of those two columns and
 // stretched to the area; columns 2.. = power split, softmax * P_sum.
-__global__ __launch_bounds__(256) void k_nu_decode(const float* __restrict__ y, float* __restrict__ out, long long rows, int D,
-                                                   float width, float height, float p_sum, const float2* __restrict__ part) {
-    // a row is 2 + K scalars (K <= a few dozen users): one thread per row
-    const long long r = blockIdx.x * 256LL + threadIdx.x;
-    if (r >= rows) return;
-    const float2 mm = part[0];
-    const float* yr = y + r * D;
+// a row is 2 + K scalars (K <= a few dozen users): one thread per row
+__device__ __forceinline__ void nu_decode_row(const float* __restrict__ yr, float* __restrict__ o, int D, float width, float height,
+                                              float p_sum, float2 mm) {
     float m = -INFINITY;
     for (int c = 2; c < D; ++c) m = fmaxf(m, yr[c]);
     float s = 0.f;
     for (int c = 2; c < D; ++c) s += expf(yr[c] - m);
-    for (int c = 2; c < D; ++c) out[r * D + c] = expf(yr[c] - m) / s * p_sum;
-    out[r * D] = (yr[0] - mm.x) / (mm.y - mm.x) * width;
-    out[r * D + 1] = (yr[1] - mm.x) / (mm.y - mm.x) * height;
+    for (int c = 2; c < D; ++c) o[c] = expf(yr[c] - m) / s * p_sum;
+    o[0] = (yr[0] - mm.x) / (mm.y - mm.x) * width;
+    o[1] = (yr[1] - mm.x) / (mm.y - mm.x) * height;
+}
+__global__ __launch_bounds__(256) void k_nu_decode(const float* __restrict__ y, float* __restrict__ out, long long rows, int D,
+                                                   float width, float height, float p_sum, const float2* __restrict__ part) {
+    const long long r = blockIdx.x * 256LL + threadIdx.x;
+    if (r >= rows) return;
+    nu_decode_row(y + r * D, out + r * D, D, width, height, p_sum, part[0]);
 }
 
 // NU objective (NU.py:279-303): NOMA successive interference cancellation.  Users ordered by channel gain, strongest
 // first; rank 0 sees only noise, rank r sees the summed power of ranks < r.  K = D - 2 <= 32 users, one thread per row.
 constexpr int kNuMaxUsers = 32;
-__global__ __launch_bounds__(256) void k_nu_rate(const float* __restrict__ Yd, const float* __restrict__ X, float* __restrict__ out,
-                                                 long long rows, int K) {
-    const long long r = blockIdx.x * 256LL + threadIdx.x;
-    if (r >= rows) return;
+__device__ __forceinline__ float nu_rate_row(const float* __restrict__ yd, const float* __restrict__ x, int K) {
     const float sigma_sq = 110.f, rou_0 = 60.f, H = 150.f;
-    const float* yd = Yd + r * (K + 2);
-    const float* x = X + r * 2 * K;
     float hg[kNuMaxUsers];
     int ord[kNuMaxUsers];
     for (int k = 0; k < K; ++k) {
@@ -241,7 +248,13 @@ __global__ __launch_bounds__(256) void k_nu_rate(const float* __restrict__ Yd, c
         else { prev += yd[2 + ord[rk - 1]]; sinr = pw / (prev + sigma_sq / h2); }
         rate += log2f(1.0f + sinr);
     }
-    out[r] = rate;
+    return rate;
+}
+__global__ __launch_bounds__(256) void k_nu_rate(const float* __restrict__ Yd, const float* __restrict__ X, float* __restrict__ out,
+                                                 long long rows, int K) {
+    const long long r = blockIdx.x * 256LL + threadIdx.x;
+    if (r >= rows) return;
+    out[r] = nu_rate_row(Yd + r * (K + 2), X + r * 2 * K, K);
 }
 
 }  // namespace dsg

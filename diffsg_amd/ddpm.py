@@ -249,6 +249,56 @@ class DDPMCore(nn.Module):
         """Post-processing of the i-th recorded state (problem specific; overridden by the problem modules)."""
         return y
 
+    def _best_of_problem(self):
+        """(problem, keyword parameters) of `repeated.best_of` for this model's problem (overridden by the problem modules)."""
+        raise NotImplementedError("sample_best: this DDPM has no decoder / objective (use a problem module's DDPM)")
+
+    @torch.no_grad()
+    def sample_best(self, cond, X, n, omega=1.0, *, seeds=None, chunk_rows=None, max_rows=65536, use_graph=True, check_range=True,
+                    return_objectives=False):
+        """Repeated sampling: `n` rounds of `sample(cond, omega)` (of `sample_chunked(cond, omega, chunk_rows)` when `chunk_rows`
+        is given), each decoded and scored against the unscaled features `X`, the best round kept per condition
+        (`repeated.best_of`; returns its `BestOf`).
+
+        A round is exactly one such call: own Philox seed(s), own early-step renormalisation.  `seeds`: one per round, or one
+        per chunk per round with `chunk_rows`, round-major (default: drawn from torch's global generator in that order).
+        Where the rounds tile into whole 32-row-aligned chunks they are sampled in groups: `cond` is repeated for as many
+        rounds as keep the launch at or below `max_rows` rows (at least one) and ONE `sample_chunked` call samples the group,
+        row for row bit-identical to the rounds' own calls.  Raw candidates of at most one group are alive at a time."""
+        from .repeated import best_of
+        if not cond.is_cuda:
+            raise RuntimeError("DDPM.sample_best: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
+        n = int(n)
+        if n < 1:
+            raise ValueError("sample_best: n must be at least 1")
+        problem, params = self._best_of_problem()
+        B = cond.shape[0]
+        one_call = chunk_rows is None or chunk_rows >= B          # a round is one sample() call (sample_chunked does the same)
+        u = B if one_call else int(chunk_rows)
+        per_round = 1 if one_call else (B + u - 1) // u
+        if seeds is None:
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(n * per_round)]
+        seeds = [int(s) for s in np.asarray(seeds, dtype=object).reshape(-1)]
+        if len(seeds) != n * per_round:
+            raise ValueError(f"sample_best: {n} rounds of {per_round} call(s) need {n * per_round} seeds, got {len(seeds)}")
+        grouped = B > 0 and u % 32 == 0 and B % u == 0
+        group = max(1, int(max_rows) // B) if grouped else 1
+        kw = dict(use_graph=use_graph, check_range=check_range)
+        running = None
+        for r0 in range(0, n, group):
+            g = min(group, n - r0)
+            sd = seeds[r0 * per_round:(r0 + g) * per_round]
+            if grouped and g > 1:
+                Y = self.sample_chunked(cond.repeat(g, 1), omega, u, seeds=sd, **kw).view(g, B, -1)
+            elif one_call:
+                Y = self.sample(cond, omega, seed=sd[0], **kw)[None]
+            elif u % 32 == 0:
+                Y = self.sample_chunked(cond, omega, u, seeds=sd, **kw)[None]
+            else:                                                  # chunks off the 32-row tile: the serial calls
+                Y = torch.cat([self.sample(cond[i * u:(i + 1) * u], omega, seed=sd[i], **kw) for i in range(per_round)])[None]
+            running = best_of(problem, Y, X, out=running, round0=r0, return_objectives=return_objectives, **params)
+        return running
+
     def op_profile(self):
         """[(name, algorithmic flops/row/step, algorithmic bytes/row/step, ms_total, launches)] of the last
         `sample(..., profile=True)` call (dsg_op_info / dsg_op_profile)."""

@@ -233,6 +233,27 @@ int dsg_nu_decode(const float* y, float* out, long long rows, int D, float width
 /* rate_calc, classifier_free_NU.py:279-303: NOMA-SIC sum rate; Yd [rows][K+2] decoded, X [rows][2K] user positions; K <= 32. */
 int dsg_nu_rate(const float* Yd, const float* X, float* rate, long long rows, int K, void* stream);
 
+/* ---- Repeated sampling: the best of n candidate rows per condition, chosen on the device (csrc/dsg_best.hpp).
+ * Y [n][B][D] raw sampler output of n rounds, round-major.  Each round is decoded as the problem's decoder decodes a [B][D]
+ * tensor (MSR, NU: min-max over that round only; CO: dead-row rule) and each decoded row gets the problem's objective:
+ *   MSR  solution = W * msr_decode row,  objective = sum rate against the gains X [B][D]           (maximised), params = {W}
+ *   CO   solution = co_decode row,       objective = cost against X [B][3D]                        (minimised), params = NULL
+ *   NU   solution = nu_decode row,       objective = NOMA rate against X [B][2(D-2)]               (maximised), params = {width,
+ *        height, p_sum}
+ * (`params` is read on the host during the call).  Per condition the round with the strictly best FINITE objective wins, the
+ * lowest round on equal objectives; solution [B][D], objective [B] and round [B] receive the winner's decoded row, objective
+ * and index.  If no round of a condition is finite, round = -1 and solution / objective are round 0's.  objectives, if not
+ * NULL, receives every round's objective [n][B].  Every per-round value is bit-identical to what the decoder / evaluator
+ * calls above return for that round.  accumulate != 0: solution / objective / round hold an earlier result; only a strictly
+ * better candidate replaces it (a stored -1 is replaced by any finite one) and its index is stored as round0 + k, so a
+ * caller can work through the rounds in groups.  n * B <= 2^31 - 1; MSR D <= 1024, CO D <= 16, NU 3 <= D <= 34.
+ * B == 0 or n == 0 launches nothing.  Stream-ordered. */
+#define DSG_PROBLEM_MSR 0
+#define DSG_PROBLEM_CO 1
+#define DSG_PROBLEM_NU 2
+int dsg_best_of(int problem, const float* Y, const float* X, int n, long long B, int D, const float* params, float* solution,
+                float* objective, int* round, float* objectives, int accumulate, int round0, void* stream);
+
 /* ---- Label generator of the MSR problem: SUM_RATE_GEN, utils/dataset_generate.py:280-313 ("LRH gradient
  * descent", float64 like the reference).  gs [rows][M] channel gains (the reference draws them with np.random.uniform; the
  * caller does), W total power; schemes [rows][M] and rates [rows] are written.  M <= 128.  Stream-ordered. */
