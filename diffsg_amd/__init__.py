@@ -7,5 +7,6 @@ from .UNetCF import UNet1D  # noqa: F401
 from .diffusion import generate_cosine_schedule, init_weights  # noqa: F401
 from .ema import ExponentialMovingAverage  # noqa: F401
 from .repeated import BestOf, best_of  # noqa: F401
+from .mtfnn import MTFNN, co_net, msr_net  # noqa: F401
 
-__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of"]
+__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of", "MTFNN", "co_net", "msr_net"]

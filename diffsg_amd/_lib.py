@@ -52,6 +52,10 @@ def built_id():
 MAX_RES = 8
 
 
+class MlpDesc(ctypes.Structure):
+    _fields_ = [("n_layers", ctypes.c_int), ("widths", ctypes.c_int * 6), ("n_sig", ctypes.c_int)]
+
+
 class UNetDesc(ctypes.Structure):
     _fields_ = [("input_dim", ctypes.c_int), ("proj_dim", ctypes.c_int), ("cond_dim", ctypes.c_int),
                 ("n_res", ctypes.c_int), ("dims", ctypes.c_int * MAX_RES), ("n_blocks", ctypes.c_int)]
@@ -198,6 +202,14 @@ _SIGS = {
                                            ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     "dsg_noma_uav_search": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    "dsg_mlp_param_total": (ctypes.c_int, [ctypes.POINTER(MlpDesc)]),
+    "dsg_mlp_forward": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                       ctypes.c_void_p]),
+    "dsg_mlp_loss_grad": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dsg_mlp_train_epoch": (ctypes.c_int, [ctypes.POINTER(MlpDesc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p]),
     "dsg_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong,
                                   ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_void_p]),

@@ -15,6 +15,7 @@
 #include "dsg_labelgen.hpp"
 #include "dsg_cogen.hpp"
 #include "dsg_nugen.hpp"
+#include "dsg_mlp.hpp"
 #include "../../include/diffsg.h"
 
 #include <math.h>
@@ -3314,6 +3315,118 @@ int dsg_box_calibrate(float* out3 /* four floats */, void* stream) {
                                              reinterpret_cast<const uint4*>(buf + copy_bytes), copy_bytes / 16 - 1, panels, sink); }, msp)) return 1;
         out3[3] = (float)((double)cus * 8 * panels * 48 / (msp * 1e-3) / 1e9);
     }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- MTFNN baseline (dsg_mlp.hpp)
+namespace {
+// Validates the descriptor and lays the workgroup's LDS out: scalar slots | parameters | tile area (activations of every layer, targets)
+// [| gradient | exp_avg | exp_avg_sq when `epoch` and they fit].  The tile height depends on the net's shape alone, so that
+// dsg_mlp_loss_grad and dsg_mlp_train_epoch sum a batch's rows in the same order.
+int mlp_plan(const dsg_mlp_desc* d, MlpPlan* p, bool epoch, const char* who) {
+    if (!d) return fail("%s: null descriptor", who);
+    const int L = d->n_layers;
+    if (L < 2 || L > kMlpMaxLayers) return fail("%s: %d Linear layers (2 .. %d)", who, L, kMlpMaxLayers);
+    for (int l = 0; l <= L; ++l) {
+        const int lim = (l == 0 || l == L) ? kMlpMaxIO : kMlpMaxHidden;
+        if (d->widths[l] < 1 || d->widths[l] > lim)
+            return fail("%s: widths[%d] = %d (%s width 1 .. %d)", who, l, d->widths[l], (l == 0 || l == L) ? "input / output" : "hidden", lim);
+    }
+    if (d->n_sig < 0 || d->n_sig > d->widths[L]) return fail("%s: n_sig = %d with %d output columns", who, d->n_sig, d->widths[L]);
+    memset(p, 0, sizeof *p);
+    p->L = L;
+    p->n_sig = d->n_sig;
+    int off = 0, row = 0;
+    for (int l = 0; l <= L; ++l) p->w[l] = d->widths[l];
+    for (int l = 0; l < L; ++l) {
+        p->woff[l] = off; off += p->w[l + 1] * p->w[l];
+        p->boff[l] = off; off += p->w[l + 1];
+    }
+    p->P = off;
+    for (int l = 0; l <= L; ++l) row += p->w[l] | 1;
+    row += p->w[L] | 1;                                   // the targets
+    int TR = 64;
+    while (TR > 16 && kMlpScal + p->P + TR * row > kMlpLdsFloats) TR >>= 1;
+    if (kMlpScal + p->P + TR * row > kMlpLdsFloats) return fail("%s: the net does not fit in LDS", who);   // not reachable within the width limits
+    p->TR = TR;
+    p->tr_shift = TR == 64 ? 6 : (TR == 32 ? 5 : 4);
+    int a = 0;
+    for (int l = 0; l <= L; ++l) { p->aoff[l] = a; p->astr[l] = p->w[l] | 1; a += TR * p->astr[l]; }
+    p->yoff = a; p->ystr = p->w[L] | 1; a += TR * p->ystr;
+    p->act_floats = a;
+    p->lds_floats = kMlpScal + p->P + a;
+    p->onchip = epoch && p->lds_floats + 3 * p->P <= kMlpLdsFloats;
+    if (p->onchip) p->lds_floats += 3 * p->P;
+    return 0;
+}
+template <typename K>
+int mlp_lds_attr(K kernel, int bytes) {
+    if (bytes > 65536) HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int dsg_mlp_param_total(const dsg_mlp_desc* desc) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_param_total")) return -1;
+    return p.P;
+}
+
+int dsg_mlp_forward(const dsg_mlp_desc* desc, const float* params, const float* x, float* out, long long rows, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_forward")) return 1;
+    if (rows < 0) return fail("dsg_mlp_forward: rows = %lld", rows);
+    if (rows == 0) return 0;
+    if (!params || !x || !out) return fail("dsg_mlp_forward: null argument");
+    const int bytes = p.lds_floats * 4;
+    if (mlp_lds_attr(k_mlp_forward, bytes)) return 1;
+    const long long ntiles = (rows + p.TR - 1) / p.TR;
+    hipLaunchKernelGGL(k_mlp_forward, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x,
+                       out, rows);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int dsg_mlp_loss_grad(const dsg_mlp_desc* desc, const float* params, const float* x, const float* y, long long rows, float* loss_out,
+                      float* grad_flat, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_loss_grad")) return 1;
+    if (rows < 0 || rows > 2147483647LL / kMlpMaxIO) return fail("dsg_mlp_loss_grad: rows = %lld (0 .. %lld)", rows, 2147483647LL / kMlpMaxIO);
+    if (rows == 0) return 0;
+    if (!params || !x || !y || !loss_out || !grad_flat) return fail("dsg_mlp_loss_grad: null argument");
+    const int bytes = p.lds_floats * 4;
+    if (mlp_lds_attr(k_mlp_loss_grad, bytes)) return 1;
+    hipLaunchKernelGGL(k_mlp_loss_grad, dim3(1), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x, y, (int)rows, loss_out, grad_flat);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
+                        const int* perm, int N, int batch, double lr, double beta1, double beta2, double eps, long long step0, float* batch_loss,
+                        int R, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, true, "dsg_mlp_train_epoch")) return 1;
+    if (N < 0 || batch < 1 || R < 1 || step0 < 0) return fail("dsg_mlp_train_epoch: N = %d, batch = %d, R = %d, step0 = %lld", N, batch, R, step0);
+    if (N > 2147483647 / kMlpMaxIO) return fail("dsg_mlp_train_epoch: N = %d rows (at most %d)", N, 2147483647 / kMlpMaxIO);
+    if (N == 0) return 0;
+    if (!params || !exp_avg || !exp_avg_sq || !X || !Y || !perm || !batch_loss) return fail("dsg_mlp_train_epoch: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    MlpEpochArgs e{params, exp_avg, exp_avg_sq, nullptr, X, Y, perm, batch_loss, N, batch, (int)(((long long)N + batch - 1) / batch),
+                   lr, beta1, beta2, eps, step0};
+    const int bytes = p.lds_floats * 4;
+    if (mlp_lds_attr(k_mlp_epoch, bytes)) return 1;
+    // nets whose gradient and moments do not fit in LDS: the gradient in stream-ordered scratch (as the evaluators' reductions); nothing
+    // between the allocation and its release returns early
+    if (!p.onchip) HIPCK(hipMallocAsync(reinterpret_cast<void**>(&e.gws), (size_t)R * p.P * sizeof(float), s));
+    hipLaunchKernelGGL(k_mlp_epoch, dim3((unsigned)R), dim3(kMlpThreads), bytes, s, p, e);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t freed = e.gws ? hipFreeAsync(e.gws, s) : hipSuccess;
+    HIPCK(launched);
+    HIPCK(freed);
     return 0;
 }
 

@@ -1411,10 +1411,14 @@ struct AdamArgs {
 };
 __device__ __forceinline__ void adam_one(float& param, float grad, float& exp_avg, float& exp_avg_sq, const AdamArgs& a, float bias_correction1,
                                          float bias_correction2_sqrt) {
+    // The fused multiply-adds are written out (and contraction is off) exactly as k_adam has always been compiled, so that the function
+    // gives the same bits in every kernel it is inlined into (k_mlp_epoch, csrc/dsg_mlp.hpp): left to the compiler, which product of
+    // `beta * moment + (1 - beta) * grad` joins the sum in one rounding depends on the surrounding code.
+#pragma clang fp contract(off)
     if (a.maximize) grad = -grad;
-    if (a.weight_decay != 0) grad += param * a.weight_decay;
-    exp_avg = a.beta1 * exp_avg + (1 - a.beta1) * grad;
-    exp_avg_sq = a.beta2 * exp_avg_sq + (1 - a.beta2) * grad * grad;
+    if (a.weight_decay != 0) grad = fma(a.weight_decay, (double)param, (double)grad);
+    exp_avg = fma(a.beta1, (double)exp_avg, (1 - a.beta1) * grad);
+    exp_avg_sq = fma(a.beta2, (double)exp_avg_sq, (1 - a.beta2) * grad * grad);
     const float step_size = a.lr / bias_correction1;
     const float denom = (sqrtf(exp_avg_sq) / bias_correction2_sqrt) + a.eps;
     param -= step_size * exp_avg / denom;

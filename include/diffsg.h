@@ -278,6 +278,38 @@ int dsg_co_minlp_search(const double* params, const double* choices, int nch, do
 int dsg_noma_uav_search(const double* qs, const double* fs, int nfs, double* out, long long rows, double sigma_sq, double rou_0,
                         double H, void* stream);
 
+/* ---- The MTFNN baseline (baselines/MTFNN.py: class MTFNN and the inline nets of mtfnn_co / mtfnn_msr), csrc/dsg_mlp.hpp.
+ * A plain MLP: n_layers Linear layers (2 .. 5), ReLU after every layer but the last, then a head: sigmoid on output columns
+ * [0, n_sig), one softmax (torch.softmax(dim=1), what the reference's bare nn.Softmax() resolves to on 2-D input) over the rest.
+ * n_sig = out gives the CO net, 0 the MSR net, 2 the NU net.  widths[0] = inputs ... widths[n_layers] = outputs; input and output
+ * width <= 128, hidden widths <= 64; anything else is refused.  Parameters (and gradients, Adam moments) travel as ONE flat float32
+ * vector in state-dict order: lin1.weight ([out][in] row-major), lin1.bias, lin2.weight, ...  No handle.  Stream-ordered; rows == 0
+ * (N == 0) launches nothing. */
+typedef struct {
+    int n_layers;
+    int widths[6];
+    int n_sig;
+} dsg_mlp_desc;
+/* Length of the flat parameter vector, or -1 (message in the last error) if the descriptor is refused. */
+int dsg_mlp_param_total(const dsg_mlp_desc* desc);
+/* out[rows][out_dim] = net(x[rows][in_dim]), row-parallel. */
+int dsg_mlp_forward(const dsg_mlp_desc* desc, const float* params, const float* x, float* out, long long rows, void* stream);
+/* *loss_out = mean((y - net(x))^2) over rows x out_dim (F.mse_loss) and grad_flat[P] = its gradient for every parameter, flat layout;
+ * updates nothing.  One workgroup, the rows in tiles in a fixed order: deterministic, and the per-batch arithmetic of the epoch call. */
+int dsg_mlp_loss_grad(const dsg_mlp_desc* desc, const float* params, const float* x, const float* y, long long rows, float* loss_out,
+                      float* grad_flat, void* stream);
+/* One whole epoch in one launch (the reference's loop over a shuffling DataLoader, MTFNN.py:60-73): for k = 0 .. ceil(N / batch) - 1 the
+ * rows perm[k * batch .. min((k + 1) * batch, N)) of X [N][in_dim] / Y [N][out_dim] (gathered on the fly; perm is int32 on the device,
+ * entries in [0, N) -- the kernel clamps them so that a bad entry cannot read outside X), forward, MSE over the batch's own rows,
+ * backward, and one Adam step (torch.optim.Adam, no weight decay) numbered step0 + k + 1; batch_loss[k] receives the batch's mean loss.
+ * R >= 1 independent models train in the same launch on the same X / Y, one workgroup each: params, exp_avg, exp_avg_sq [R][P],
+ * perm [R][N], batch_loss [R][ceil(N / batch)].  No floating-point atomics, every sum over rows in one fixed order: run-to-run
+ * identical, replica r identical to an R = 1 call on its slices, and every batch bit-identical to dsg_mlp_loss_grad on the gathered
+ * rows followed by dsg_adam_step. */
+int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
+                        const int* perm, int N, int batch, double lr, double beta1, double beta2, double eps, long long step0,
+                        float* batch_loss, int R, void* stream);
+
 /* Measurement hooks for bench.py: the per-step operator list and a timed replay of one operator's kernel with HIP
  * events on `stream` (rows = B rows, both passes, as inside dsg_sample). */
 int dsg_op_count(const dsg_handle* h);
