@@ -16,6 +16,7 @@
 #include "dsg_cogen.hpp"
 #include "dsg_nugen.hpp"
 #include "dsg_mlp.hpp"
+#include "dsg_own.hpp"
 #include "../../include/diffsg.h"
 
 #include <math.h>
@@ -136,7 +137,20 @@ constexpr int kPanelMinTilesDefault = 768;
 constexpr int kMaxWgParts = 8;      // early parts of the weight-gradient launch (dsg_train_step)
 constexpr int kWgForkMinTiles = 1024;
 
+// Ownership: every device buffer, stream, event and graph executable the handle creates is a member of an owning type (dsg_own.hpp)
+// and is released by `delete h`.  Members are destroyed in reverse order of declaration, and the order below is the one that needs:
+// the pinned word, the events and the streams come first (destroyed last, after everything enqueued on them is gone), then the
+// buffers -- the forward workspace `fw` before the training workspace `tr`, whose descriptor tables point into `fw` -- and the graph
+// executables last (destroyed first: their nodes hold buffer addresses and were captured on cap_stream).
+// Raw pointers are NOT owned: range_flag, renorm_stats, bound_ptrs, Param::ptr and the *_key cache keys.
 struct dsg_handle {
+    PinnedBuf<int> range_pinned;    // pinned host word dsg_range_status_stream reads the flag through
+    Event tev[6];                   // dsg_train_profile_enable: the phase boundaries of dsg_train_step
+    Event ev_fork, ev_join;
+    Event ev_tail[3];               // the tail of dsg_train_step: chain done / time path done / column sums done
+    Stream cap_stream;              // capture-only stream (the caller's may be the null stream)
+    Stream side_stream;
+
     dsg_unet_desc d;
     int td = 0;  // time_dim = 4*proj
     std::vector<Param> params;
@@ -151,13 +165,13 @@ struct dsg_handle {
     int temb_l1w, temb_l1b, temb_l2w, temb_l2b;
 
     // packed-weight arena
-    float* arena = nullptr;
+    DevBuf<float> arena;
     size_t arena_floats = 0;
-    TimeBlockDesc* tdesc_dev = nullptr;
-    PackDesc* pack_dev = nullptr;
+    DevBuf<TimeBlockDesc> tdesc_dev;
+    DevBuf<PackDesc> pack_dev;
     int pack_n = 0;
     long long pack_blocks = 0;
-    std::vector<const float*> bound_ptrs;
+    std::vector<const float*> bound_ptrs;   // the caller's tensors (not owned)
     bool bound = false;
 
     // fp16-split path (dsg_split.hpp): wide blocks of the sampling loop
@@ -169,64 +183,63 @@ struct dsg_handle {
     // one 8-wave workgroup per CU); coop_max_tiles == 0 ("every launch takes its large-launch form") lowers it to 0
     int panel_min_tiles = kPanelMinTilesDefault;
     int num_cus = 256;
-    float* maxabs = nullptr;           // [params]: max|W| per tensor, refreshed at every bind
-    const float** mx_ptrs_dev = nullptr; long long* mx_numel_dev = nullptr; int* mx_idx_dev = nullptr; int mx_n = 0;
+    DevBuf<float> maxabs;              // [params]: max|W| per tensor, refreshed at every bind
+    DevBuf<const float*> mx_ptrs_dev; DevBuf<long long> mx_numel_dev; DevBuf<int> mx_idx_dev; int mx_n = 0;
     std::vector<int> mx_param;         // param index of each k_maxabs block
-    PackHDesc* packh_dev = nullptr; int packh_n = 0; long long packh_blocks = 0;
-    OpConstDesc* opc_desc_dev = nullptr; float* opc_dev = nullptr;   // [res | lin][4]: un-scale factors, refreshed at every bind (k_pack_h)
+    DevBuf<PackHDesc> packh_dev; int packh_n = 0; long long packh_blocks = 0;
+    DevBuf<OpConstDesc> opc_desc_dev; DevBuf<float> opc_dev;   // [res | lin][4]: un-scale factors, refreshed at every bind (k_pack_h)
 
-    // forward workspace
+    // forward workspace (ensure_workspace: sized for cap_rows rows and cap_entries schedule entries)
     int cap_rows = 0, cap_entries = 0;
-    float* ws = nullptr;        // activations
-    float* condfrag = nullptr;
-    float* cembed = nullptr;    // [tiles_per_pass cap][ce_per_tile]: Wc silu(cond) of every block (sampling)
-    float* ce_stats = nullptr;  // scratch statistics sink of the precompute launches
+    struct FwdWorkspace {
+        DevBuf<float> ws;           // activations
+        DevBuf<float> condfrag;
+        DevBuf<float> cembed;       // [tiles_per_pass cap][ce_per_tile]: Wc silu(cond) of every block (sampling)
+        DevBuf<float> ce_stats;     // scratch statistics sink of the precompute launches
+        DevBuf<float> tb;           // [entries][tb_stride]
+        DevBuf<float> st;           // [entries][td]
+        DevBuf<float> h1s;          // [entries][td] Swish(lin1) of the time MLP
+        DevBuf<float> tvals;        // [entries]
+        DevBuf<int> ts_ident;       // [rows] identity index
+        DevBuf<float> eps;          // [2][rows][D]
+        DevBuf<float> ywork;        // [rows][D]
+    } fw;
     size_t ce_per_tile = 0;
     size_t zero_off = 0;        // 128 zero floats in the arena
-    float* tb = nullptr;        // [entries][tb_stride]
-    float* st = nullptr;        // [entries][td]
-    float* h1s = nullptr;       // [entries][td] Swish(lin1) of the time MLP
-    float* tvals = nullptr;     // [entries]
-    int* ts_ident = nullptr;    // [rows] identity index
-    float* eps = nullptr;       // [2][rows][D]
-    float* ywork = nullptr;     // [rows][D]
-    float* freq = nullptr;      // [proj/2]
-    double* red = nullptr;      // [2][kRedBlocks]
-    int* step_dev = nullptr;
-    double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device), reduced across ranks by `renorm_fn`
+    DevBuf<float> freq;         // [proj/2]
+    DevBuf<double> red;         // [2][kRedBlocks]
+    DevBuf<int> step_dev;
+    double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device, not owned), reduced across ranks by `renorm_fn`
     void (*renorm_fn)(void*) = nullptr; void* renorm_user = nullptr;
     int device = 0;              // the device that was current in dsg_create: the settings / status entry points select it themselves
-    int* range_flag = nullptr;   // device word: a raw split-path operand left fp16's range since the last dsg_range_status
-    int* range_pinned = nullptr; // pinned host word dsg_range_status_stream reads the flag through
-    CallParams* call_dev = nullptr;
-    hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the null stream)
+    int* range_flag = nullptr;   // device word: a raw split-path operand left fp16's range since the last dsg_range_status (an alias into step_dev)
+    DevBuf<CallParams> call_dev;
     std::vector<double> op_ms;   // DSG_SAMPLE_PROFILE: summed HIP-event time per op
     bool train_prof = false;     // dsg_train_profile_enable: HIP events at the phase boundaries of dsg_train_step
-    hipEvent_t tev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool tev_valid = false;
     std::vector<int> op_calls;
 
     // fused narrow run [fuse_lo, fuse_hi) of `ops` (inference only)
     int fuse_lo = 0, fuse_hi = 0;
-    FusedOp* fused_dev = nullptr;
+    DevBuf<FusedOp> fused_dev;
     std::vector<FusedOp> fused_host;
-    FusedOpH* fusedh_dev = nullptr;
+    DevBuf<FusedOpH> fusedh_dev;
     // operator table of the WHOLE net for k_unet_tile (dsg_tile.hpp: one launch per pass for small batches), rebuilt with the fused
     // narrow run's table; tile_valid: the net has the shapes the kernel covers; opt_tile: dsg_set_option(DSG_OPT_TILE_STEP)
-    FusedOpH* tileops_dev = nullptr;
+    DevBuf<FusedOpH> tileops_dev;
     std::vector<FusedOpH> tileops_host;
     bool tile_valid = false, opt_tile = true;
     bool opt_panel_half = true;       // dsg_set_option(DSG_OPT_PANEL_HALF): the 128-wide panel kernels with 16 KiB panels, two workgroups per CU
-    FusedOpH* fusedh_train_dev = nullptr;   // the same run for the training forward (every output stored, h1/h2 saved)
+    DevBuf<FusedOpH> fusedh_train_dev;      // the same run for the training forward (every output stored, h1/h2 saved)
     const void* fusedh_train_key[4] = {nullptr, nullptr, nullptr, nullptr}; int fusedh_train_rows = 0;
     // inference tables (dsg_sample / dsg_unet_forward / dsg_time_op share them): what the device copy was built for
     struct FusedSig { bool valid = false, sp = false, share = false; int nrows = 0, npass = 0, uncond_tiles = 0; const void* p[8] = {}; } fused_sig;
-    FusedOp* ce_dev = nullptr;          // condition-embedding Linear table (narrow blocks, one launch)
+    DevBuf<FusedOp> ce_dev;             // condition-embedding Linear table (narrow blocks, one launch)
     std::vector<FusedOp> ce_host;
-    CondTile* ctile_dev = nullptr; int ctile_n = 0; const float* ctile_key = nullptr; size_t ctile_cap = 0;
+    DevBuf<CondTile> ctile_dev; int ctile_n = 0; const float* ctile_key = nullptr; size_t ctile_cap = 0;
     std::vector<FusedOpH> fusedh_host;
     // LDS-resident form of the narrow run (k_fused_narrow_lds): per-operator LDS offsets, the copy list of every phase, the phases
-    NarrowLdsOp* nlds_ops_dev = nullptr; NarrowLdsCopy* nlds_copies_dev = nullptr; uint4* nlds_image = nullptr;
+    DevBuf<NarrowLdsOp> nlds_ops_dev; DevBuf<NarrowLdsCopy> nlds_copies_dev; DevBuf<uint4> nlds_image;
     std::vector<NarrowPhaseArgs> nlds_phases;
     bool nlds_tail = false;            // the LDS form of the run also computes the 64-wide Linear at ops[fuse_hi] (kind 2)
     bool nlds_valid = false;
@@ -239,57 +252,60 @@ struct dsg_handle {
     bool opt_wg_narrow_part = false;   // dsg_set_option(DSG_OPT_WGRAD_NARROW_PART); read when the descriptor tables are (re)built
     // the section's image in global memory (V8SecL layout: raw nn.Linear matrices and parameter vectors), gathered at every bind; the LDS
     // form of the narrow run stages it as one piece, small launches and the training forward read it from L1 / L2
-    float* v8_image = nullptr; NarrowLdsCopy* v8_copies_dev = nullptr; int v8_ncopies = 0;
+    DevBuf<float> v8_image; DevBuf<NarrowLdsCopy> v8_copies_dev; int v8_ncopies = 0;
     int nlds_ncopies = 0;              // entries of nlds_copies_dev: dsg_bind_weights re-gathers the image from the re-packed arena
     size_t nlds_image_cap = 0;         // uint4 capacity of nlds_image (grow-only: captured graphs hold the pointer)
 
-    // cached step graphs: per-step pair (with / without the renorm kernels), keyed by (rows, chunks); and ONE graph of a whole
-    // T-step loop for short schedules, keyed by (rows, chunks, T)
-    // captured reverse steps of the current workspace shape: gexec[0] = one early (renorm) step, gexec[1 + k] = 2^k later steps
-    hipGraphExec_t gexec[1 + 6] = {};
-    int g_rows = -1, g_chunks = -1, g_chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
     // chunked calls (dsg_sample_chunked): per-chunk Philox seeds and per-chunk renorm partials
-    unsigned long long* seeds_dev = nullptr; int seeds_cap = 0;
-    double* red_chunks = nullptr; int red_chunks_cap = 0;
+    DevBuf<unsigned long long> seeds_dev; int seeds_cap = 0;
+    DevBuf<double> red_chunks; int red_chunks_cap = 0;
 
     // training workspace
     size_t tr_per_tile = 0;      // floats per tile
     size_t tr_yt_frag = 0, tr_deps = 0;
     int tr_rows = 0, tr_T = 0, tr_chunks = 0;
-    float* tr_ws = nullptr;
-    float* tr_slabs = nullptr;   // [chunks][slab_stride]
-    float* tr_gsum = nullptr;    // [slab_stride]
-    unsigned* tr_gmax = nullptr; // max|G| per gradient tensor (float bits)
-    unsigned* tr_gmax_t = nullptr; // [kMaxGmax][gmax_ld] per-tile words, zeroed every step
+    struct TrainWorkspace {      // ensure_train_workspace / build_train_descs: sized for tr_rows rows and tr_T schedule entries
+        DevBuf<float> ws;
+        DevBuf<float> slabs;         // [chunks][slab_stride]
+        DevBuf<float> gsum;          // [slab_stride]
+        DevBuf<unsigned> gmax;       // max|G| per gradient tensor (float bits)
+        DevBuf<unsigned> gmax_t;     // [kMaxGmax][gmax_ld] per-tile words, zeroed every step
+        DevBuf<float> cs;            // per block: [tiles][cs_stride of the block] column sums
+        DevBuf<int4> cs_map_dev;     // [cs_slots] (slab destination, second destination, region base + slot, row stride)
+        DevBuf<int> ts;              // [rows]
+        DevBuf<float> noise, mask;   // [rows][D], [rows]: device-side draws (dsg_train_step_seeded), allocated on first use
+        DevBuf<float> yt_rm;         // [rows][D]
+        DevBuf<float> tsave;         // emb | h1pre | h1s | tpre | d_st | d_h1s
+        DevBuf<WgradDesc> wg_desc_dev; DevBuf<WgradUnit> wg_unit_dev;
+        DevBuf<ColsumDesc> cs_desc_dev; DevBuf<ColsumUnit> cs_unit_dev;
+    } tr;
     int gmax_ld = 0;
-    float* tr_cs = nullptr;      // per block: [tiles][cs_stride of the block] column sums
-    int4* cs_map_dev = nullptr;  // [cs_slots] (slab destination, second destination, region base + slot, row stride)
     int cs_slots = 0;
     int n_gmax = 0;
     size_t slab_stride = 0;
-    int* tr_ts = nullptr;        // [rows]
-    float* tr_noise = nullptr; float* tr_mask = nullptr;   // [rows][D], [rows]: device-side draws (dsg_train_step_seeded), allocated on first use
-    float* tr_yt_rm = nullptr;   // [rows][D]
-    float* tr_tsave = nullptr;   // emb | h1pre | h1s | tpre | d_st | d_h1s
-    long long* tw_dst_dev = nullptr; const float** tw_src_dev = nullptr; int tw_rows = 0;  // time_emb.weight rows of all blocks
-    WgradDesc* wg_desc_dev = nullptr; WgradUnit* wg_unit_dev = nullptr; int wg_units = 0;
+    DevBuf<long long> tw_dst_dev; DevBuf<const float*> tw_src_dev; int tw_rows = 0;  // time_emb.weight rows of all blocks
+    int wg_units = 0;
     // early parts of the weight-gradient launch: after the backward kernel of residual block number wg_forks[k] (counted from the
     // LAST block, the first one the backward reaches) the weight gradients of the blocks since the previous fork run on
     // side_stream beside the rest of the activation-gradient chain, see dsg_train_step
     std::vector<int> wg_forks = {3, 6};
     std::vector<int> wg_part_end;      // units [wg_part_end[k-1], wg_part_end[k]) = part k; the rest runs on the caller's stream
-    long long* r2_dev = nullptr; int r2_n = 0; long long r2_total = 0;   // [starts | prefix]: the parameter ranges the last reduce covers
+    DevBuf<long long> r2_dev; int r2_n = 0; long long r2_total = 0;   // [starts | prefix]: the parameter ranges the last reduce covers
     bool r2_vec4 = false;              // ... in float4 units (k_reduce_ranges4)
     int wg_onehot_end = 0;             // ... and opens with the final part's time-table units: [wg_part_end.back(), wg_onehot_end),
     int wg_blocks_end = 0;             // then its residual blocks' other units [wg_onehot_end, wg_blocks_end), then the plain Linears'
     std::vector<int> wg_fork_ops;      // operator index after whose backward kernel part k starts
     int wg_early_lds = 40960;
-    hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_tail[3] = {nullptr, nullptr, nullptr};   // the tail of dsg_train_step: chain done / time path done / column sums done
-    FusedBwdOpH* fbwd_dev = nullptr; int fbwd_n = 0;   // operator table of the fused narrow backward (split path), cached with the descriptors
-    ColsumDesc* cs_desc_dev = nullptr; ColsumUnit* cs_unit_dev = nullptr; int cs_units = 0;
+    DevBuf<FusedBwdOpH> fbwd_dev; int fbwd_n = 0;   // operator table of the fused narrow backward (split path), cached with the descriptors
+    int cs_units = 0;
     // the descriptor tables depend only on (rows, T, precision mode) and the workspace addresses: built once, reused every step
     bool td_valid = false; int td_B = 0, td_T = 0, td_rows = 0; bool td_split = false; const void* td_key[6] = {};
+
+    // cached step graphs: per-step pair (with / without the renorm kernels), keyed by (rows, chunks); and ONE graph of a whole
+    // T-step loop for short schedules, keyed by (rows, chunks, T)
+    // captured reverse steps of the current workspace shape: gexec[0] = one early (renorm) step, gexec[1 + k] = 2^k later steps
+    GraphExec gexec[1 + 6];
+    int g_rows = -1, g_chunks = -1, g_chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
 };
 
 namespace {
@@ -438,21 +454,14 @@ void carve(dsg_handle* h) {
 }
 
 void free_graphs(dsg_handle* h) {
-    for (auto& g : h->gexec)
-        if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    for (auto& g : h->gexec) g.reset();
     h->g_rows = h->g_chunks = h->g_chunk_rows = -1;
 }
 
 constexpr int kMaxGmax = 256;   // distinct gradient tensors whose max|G| is tracked (3 per block + 1 per Linear)
 
 void free_train_workspace(dsg_handle* h) {
-    void* ptrs[] = {h->tr_ws, h->tr_slabs, h->tr_gsum, h->tr_ts, h->tr_noise, h->tr_mask, h->tr_yt_rm, h->tr_tsave, h->wg_desc_dev, h->wg_unit_dev,
-                    h->cs_desc_dev, h->cs_unit_dev, h->tr_gmax, h->tr_gmax_t, h->tr_cs, h->cs_map_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->tr_ws = h->tr_slabs = h->tr_gsum = h->tr_yt_rm = h->tr_tsave = nullptr;
-    h->tr_ts = nullptr; h->tr_noise = nullptr; h->tr_mask = nullptr; h->tr_gmax = nullptr; h->tr_gmax_t = nullptr; h->tr_cs = nullptr; h->cs_map_dev = nullptr;
-    h->wg_desc_dev = nullptr; h->wg_unit_dev = nullptr; h->cs_desc_dev = nullptr; h->cs_unit_dev = nullptr;
+    h->tr = {};
     h->wg_units = h->cs_units = 0;
     h->tr_rows = h->tr_T = 0;
     h->td_valid = false;
@@ -462,12 +471,7 @@ void free_workspace(dsg_handle* h) {
     h->fused_sig.valid = false;
     free_graphs(h);
     free_train_workspace(h);  // its descriptors point into the forward workspace
-    void* ptrs[] = {h->ws, h->condfrag, h->tb, h->st, h->tvals, h->ts_ident, h->eps, h->ywork, h->cembed, h->ce_stats, h->h1s};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->cembed = h->ce_stats = h->h1s = nullptr;
-    h->ws = h->condfrag = h->tb = h->st = h->tvals = h->eps = h->ywork = nullptr;
-    h->ts_ident = nullptr;
+    h->fw = {};
     h->cap_rows = h->cap_entries = 0;
 }
 
@@ -490,19 +494,19 @@ int ensure_workspace(dsg_handle* h, int rows, int entries) {
     free_workspace(h);
     const size_t tiles = (size_t)cdiv(nrows, 32) * 2;  // two passes
     const int D = h->d.input_dim, CG = groups_of(h->d.cond_dim);
-    HIPCK(hipMalloc(&h->ws, tiles * h->per_tile_floats * sizeof(float)));
-    HIPCK(hipMemset(h->ws, 0, tiles * h->per_tile_floats * sizeof(float)));
-    HIPCK(hipMalloc(&h->condfrag, (tiles / 2) * CG * 256 * sizeof(float)));
-    HIPCK(hipMalloc(&h->cembed, (tiles / 2) * h->ce_per_tile * sizeof(float)));
-    HIPCK(hipMalloc(&h->ce_stats, (tiles / 2) * 64 * sizeof(float)));
-    HIPCK(hipMalloc(&h->tb, (size_t)nent * h->tb_stride * sizeof(float)));
-    HIPCK(hipMalloc(&h->st, (size_t)nent * h->td * sizeof(float)));
-    HIPCK(hipMalloc(&h->h1s, (size_t)nent * h->td * sizeof(float)));
-    HIPCK(hipMalloc(&h->tvals, (size_t)nent * sizeof(float)));
-    HIPCK(hipMalloc(&h->ts_ident, (size_t)nrows * sizeof(int)));
-    HIPCK(hipMalloc(&h->eps, (size_t)2 * nrows * D * sizeof(float)));
-    HIPCK(hipMalloc(&h->ywork, (size_t)nrows * D * sizeof(float)));
-    hipLaunchKernelGGL(k_iota, dim3(cdiv(nrows, 256)), dim3(256), 0, 0, h->ts_ident, nrows);
+    HIPCK(h->fw.ws.alloc(tiles * h->per_tile_floats));
+    HIPCK(hipMemset(h->fw.ws, 0, tiles * h->per_tile_floats * sizeof(float)));
+    HIPCK(h->fw.condfrag.alloc((tiles / 2) * CG * 256));
+    HIPCK(h->fw.cembed.alloc((tiles / 2) * h->ce_per_tile));
+    HIPCK(h->fw.ce_stats.alloc((tiles / 2) * 64));
+    HIPCK(h->fw.tb.alloc((size_t)nent * h->tb_stride));
+    HIPCK(h->fw.st.alloc((size_t)nent * h->td));
+    HIPCK(h->fw.h1s.alloc((size_t)nent * h->td));
+    HIPCK(h->fw.tvals.alloc((size_t)nent));
+    HIPCK(h->fw.ts_ident.alloc((size_t)nrows));
+    HIPCK(h->fw.eps.alloc((size_t)2 * nrows * D));
+    HIPCK(h->fw.ywork.alloc((size_t)nrows * D));
+    hipLaunchKernelGGL(k_iota, dim3(cdiv(nrows, 256)), dim3(256), 0, 0, h->fw.ts_ident, nrows);
     HIPCK(hipDeviceSynchronize());
     h->cap_rows = nrows;
     h->cap_entries = nent;
@@ -643,14 +647,14 @@ Seg seg_of(const dsg_handle* h, int tid) {
     const TensorInfo& t = h->tensors[tid];
     const size_t cap = cap_tiles_of(h);
     Seg s;
-    s.data = h->ws + t.data_off * cap;
-    s.stats = h->ws + t.stats_off * cap;
+    s.data = h->fw.ws + t.data_off * cap;
+    s.stats = h->fw.ws + t.stats_off * cap;
     s.groups = groups_of(t.width);
     s.width = t.width;
     s.wrap = 0;
     return s;
 }
-float* trp(const dsg_handle* h, size_t off) { return h->tr_ws + off * tr_tiles_of(h); }
+float* trp(const dsg_handle* h, size_t off) { return h->tr.ws + off * tr_tiles_of(h); }
 
 void fill_block_args(const dsg_handle* h, const Op& op, const RunCtx& c, BlockArgs& a) {
     const int tpp = cdiv(c.nrows, 32);
@@ -665,15 +669,15 @@ void fill_block_args(const dsg_handle* h, const Op& op, const RunCtx& c, BlockAr
         if (op.in1 == pt) a.in1.wrap = tpp;
     }
     a.W1 = A + r.W1p; a.gamma1 = A + r.g1p; a.beta1 = A + r.b1p;
-    a.tbias = h->tb + r.tb_off; a.step_ptr = c.step_ptr; a.ts = c.ts; a.tb_stride = h->tb_stride;
+    a.tbias = h->fw.tb + r.tb_off; a.step_ptr = c.step_ptr; a.ts = c.ts; a.tb_stride = h->tb_stride;
     a.W2 = A + r.W2p; a.gamma2 = A + r.g2p; a.beta2 = A + r.b2p; a.c2 = A + r.c2p;
-    a.Wc = A + r.Wcp; a.condfrag = h->condfrag; a.cond_groups = groups_of(h->d.cond_dim);
+    a.Wc = A + r.Wcp; a.condfrag = h->fw.condfrag; a.cond_groups = groups_of(h->d.cond_dim);
     a.W3 = A + r.W3p; a.gamma3 = A + r.g3p; a.beta3 = A + r.b3p; a.c3 = A + r.c3p;
     a.Wsc = r.sclin ? A + r.Wscp : nullptr;
     const Seg o = seg_of(h, op.out);
     a.out = const_cast<float*>(o.data); a.out_stats = const_cast<float*>(o.stats);
     if (c.train) { a.save_h1 = trp(h, r.h1); a.save_h2 = trp(h, r.h2); }
-    if (c.cond_pre) a.cond_pre = h->cembed + r.ce_off * (cap_tiles_of(h) / 2);
+    if (c.cond_pre) a.cond_pre = h->fw.cembed + r.ce_off * (cap_tiles_of(h) / 2);
     a.ntiles = tpp * c.npass; a.tiles_per_pass = tpp; a.uncond_tiles = c.uncond_tiles; a.nrows = c.nrows;
     a.range_flag = h->range_flag;
     {
@@ -996,9 +1000,9 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
     if (c.train) {
         // training forward: split path only; the table depends on the workspaces and the batch, not on the step -> cached
         if (!sp) return 0;
-        const void* key[4] = {h->ws, h->tr_ws, h->cembed, h->tb};
+        const void* key[4] = {h->fw.ws, h->tr.ws, h->fw.cembed, h->fw.tb};
         if (h->fusedh_train_dev && h->fusedh_train_rows == c.nrows && !memcmp(key, h->fusedh_train_key, sizeof key)) return 0;
-        if (!h->fusedh_train_dev) HIPCK(hipMalloc(&h->fusedh_train_dev, (h->ops.size() + 1) * sizeof(FusedOpH)));
+        if (!h->fusedh_train_dev) HIPCK(h->fusedh_train_dev.alloc(h->ops.size() + 1));
         memcpy(h->fusedh_train_key, key, sizeof key);
         h->fusedh_train_rows = c.nrows;
     }
@@ -1007,7 +1011,7 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
         // no stream synchronise between calls, so the host can enqueue the next call while this one runs
         dsg_handle::FusedSig sig;
         sig.valid = true; sig.sp = sp; sig.share = c.share_proj; sig.nrows = c.nrows; sig.npass = c.npass; sig.uncond_tiles = c.uncond_tiles;
-        const void* ptrs[8] = {c.y, c.eps_out, c.step_ptr, c.ts, h->ws, h->cembed, h->tb,
+        const void* ptrs[8] = {c.y, c.eps_out, c.step_ptr, c.ts, h->fw.ws, h->fw.cembed, h->fw.tb,
                                reinterpret_cast<const void*>((size_t)h->cap_rows * 2 + (c.cond_pre ? 1 : 0))};
         memcpy(sig.p, ptrs, sizeof ptrs);
         const dsg_handle::FusedSig& o = h->fused_sig;
@@ -1132,7 +1136,7 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
         const unsigned s_u4 = (unsigned)(s_nb == 3 ? V8SecL<3>::SIZE : V8SecL<2>::SIZE) / 4, s_tb_u4 = (unsigned)(2 * s_nb + 3) * 8;
         auto close_phase = [&](int hi) {
             NarrowPhaseArgs ph;
-            ph.image = nullptr; ph.n_u4 = used; ph.tb = h->tb + (tb_first < 0 ? 0 : tb_first); ph.tb_u4 = tb_first < 0 ? 0 : (unsigned)(tb_last_end - tb_first) / 4;
+            ph.image = nullptr; ph.n_u4 = used; ph.tb = h->fw.tb + (tb_first < 0 ? 0 : tb_first); ph.tb_u4 = tb_first < 0 ? 0 : (unsigned)(tb_last_end - tb_first) / 4;
             ph.op_lo = phase_lo; ph.op_hi = hi;
             ph.v8_at = -1; ph.v8_nops = 0; ph.v8_store = 0; ph.v8_sec = 0; ph.v8_tb = 0;
             if (s_lo >= phase_lo && s_lo < hi) {       // the float32 section lies in this phase (its image offset was noted when it was taken)
@@ -1244,13 +1248,13 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
         if (fits && n > 0) {
             close_phase(n_all);
             const size_t image_u4 = image_base;
-            if (!h->nlds_ops_dev) HIPCK(hipMalloc(&h->nlds_ops_dev, (h->ops.size() + 1) * sizeof(NarrowLdsOp)));
-            if (!h->nlds_copies_dev) HIPCK(hipMalloc(&h->nlds_copies_dev, (h->ops.size() + 1) * 16 * sizeof(NarrowLdsCopy)));
+            if (!h->nlds_ops_dev) HIPCK(h->nlds_ops_dev.alloc(h->ops.size() + 1));
+            if (!h->nlds_copies_dev) HIPCK(h->nlds_copies_dev.alloc((h->ops.size() + 1) * 16));
             if (image_u4 + 1 > h->nlds_image_cap) {
                 // grow-only: the captured step graphs hold the image pointer (phase arguments are passed by value); when it has
                 // to move, every graph captured with the old one goes (nothing is in flight: the stream was synchronised above)
-                if (h->nlds_image) { (void)hipFree(h->nlds_image); free_graphs(h); }
-                HIPCK(hipMalloc(&h->nlds_image, (image_u4 + 1) * sizeof(uint4)));
+                if (h->nlds_image) { h->nlds_image.reset(); free_graphs(h); }
+                HIPCK(h->nlds_image.alloc(image_u4 + 1));
                 h->nlds_image_cap = image_u4 + 1;
             }
             HIPCK(hipMemcpy(h->nlds_ops_dev, lops.data(), n_all * sizeof(NarrowLdsOp), hipMemcpyHostToDevice));
@@ -1401,22 +1405,22 @@ void run_unet(const dsg_handle* h, const RunCtx& c, hipStream_t s) {
     }
 }
 
-// time path for `entries` t values already in h->tvals (saves for the backward when `train`)
+// time path for `entries` t values already in h->fw.tvals (saves for the backward when `train`)
 void run_time_path(dsg_handle* h, int entries, hipStream_t s, bool train = false) {
     const int half = h->d.proj_dim / 2, td = h->td;
     const Param* P = h->params.data();
     float *emb = nullptr, *h1pre = nullptr, *tpre = nullptr;
-    float* h1s = h->h1s;
+    float* h1s = h->fw.h1s;
     if (train) {
-        emb = h->tr_tsave; h1pre = emb + (size_t)h->tr_T * 2 * half; h1s = h1pre + (size_t)h->tr_T * td;
+        emb = h->tr.tsave; h1pre = emb + (size_t)h->tr_T * 2 * half; h1s = h1pre + (size_t)h->tr_T * td;
         tpre = h1s + (size_t)h->tr_T * td;
     }
     const dim3 grid(entries, cdiv(td, 16));
-    hipLaunchKernelGGL(k_time_embed1, grid, dim3(256), 2 * half * sizeof(float), s, h->tvals, h->freq, half, P[h->temb_l1w].ptr,
+    hipLaunchKernelGGL(k_time_embed1, grid, dim3(256), 2 * half * sizeof(float), s, h->fw.tvals, h->freq, half, P[h->temb_l1w].ptr,
                        P[h->temb_l1b].ptr, td, h1s, emb, h1pre);
-    hipLaunchKernelGGL(k_time_embed2, grid, dim3(256), td * sizeof(float), s, h1s, P[h->temb_l2w].ptr, P[h->temb_l2b].ptr, td, h->st, tpre);
+    hipLaunchKernelGGL(k_time_embed2, grid, dim3(256), td * sizeof(float), s, h1s, P[h->temb_l2w].ptr, P[h->temb_l2b].ptr, td, h->fw.st, tpre);
     const int nb = (int)h->res.size();
-    hipLaunchKernelGGL(k_time_table, dim3(entries, nb * 8), dim3(256), td * sizeof(float), s, h->st, td, h->tdesc_dev, nb, h->tb, h->tb_stride);
+    hipLaunchKernelGGL(k_time_table, dim3(entries, nb * 8), dim3(256), td * sizeof(float), s, h->fw.st, td, h->tdesc_dev, nb, h->fw.tb, h->tb_stride);
 }
 
 // cembed[block] = Wc silu(cond * mask) for every block from the condition fragments (one launch per block)
@@ -1424,26 +1428,26 @@ void run_cond_embed(dsg_handle* h, int B, hipStream_t s) {
     const int tpp = cdiv(B, 32), CG = groups_of(h->d.cond_dim);
     if (h->use_split && (CG + 1) / 2 <= kCondMaxSteps) {
         // split path: every block in ONE launch
-        if (h->ctile_key != h->cembed || h->ctile_cap != cap_tiles_of(h)) {
+        if (h->ctile_key != h->fw.cembed || h->ctile_cap != cap_tiles_of(h)) {
             std::vector<CondTile> tab;
             for (const ResP& r : h->res) {
                 const int NG = groups_of(r.N);
                 for (int lt = 0; lt < cdiv(r.N, 32); ++lt) {
                     CondTile t;
-                    t.out = h->cembed + r.ce_off * (cap_tiles_of(h) / 2) + (size_t)lt * 4 * 256;
+                    t.out = h->fw.cembed + r.ce_off * (cap_tiles_of(h) / 2) + (size_t)lt * 4 * 256;
                     t.m = h->maxabs + r.ce.w;
                     t.groups = NG - 4 * lt < 4 ? NG - 4 * lt : 4;
                     t.ng_block = NG;
                     tab.push_back(t);
                 }
             }
-            if (!h->ctile_dev) (void)hipMalloc(&h->ctile_dev, tab.size() * sizeof(CondTile));
+            if (!h->ctile_dev) (void)h->ctile_dev.alloc(tab.size());
             (void)hipMemcpy(h->ctile_dev, tab.data(), tab.size() * sizeof(CondTile), hipMemcpyHostToDevice);
-            h->ctile_n = (int)tab.size(); h->ctile_key = h->cembed; h->ctile_cap = cap_tiles_of(h);
+            h->ctile_n = (int)tab.size(); h->ctile_key = h->fw.cembed; h->ctile_cap = cap_tiles_of(h);
         }
         // enough waves for ~2 per SIMD: row tiles x parts
         const int parts = tpp >= 2048 ? 1 : (tpp >= 1024 ? 2 : (tpp >= 512 ? 4 : 8));
-        hipLaunchKernelGGL(k_cond_embed_h, dim3(cdiv(tpp, kWavesPerBlock), parts), dim3(256), 0, s, h->condfrag, CG,
+        hipLaunchKernelGGL(k_cond_embed_h, dim3(cdiv(tpp, kWavesPerBlock), parts), dim3(256), 0, s, h->fw.condfrag, CG,
                            reinterpret_cast<const uint4*>(h->arena + h->res[0].Wch), h->ctile_dev, h->ctile_n, tpp);
         return;
     }
@@ -1453,10 +1457,10 @@ void run_cond_embed(dsg_handle* h, int B, hipStream_t s) {
     for (const ResP& r : h->res) {
         LinArgs a;
         memset(&a, 0, sizeof a);
-        a.in.data = h->condfrag; a.in.groups = CG; a.in.width = h->d.cond_dim;
+        a.in.data = h->fw.condfrag; a.in.groups = CG; a.in.width = h->d.cond_dim;
         a.in_width = h->d.cond_dim; a.in_groups = CG;
         a.W = h->arena + r.Wcp; a.bias = h->arena + h->zero_off;
-        a.out = h->cembed + r.ce_off * (cap_tiles_of(h) / 2); a.out_stats = h->ce_stats; a.out_width = r.N;
+        a.out = h->fw.cembed + r.ce_off * (cap_tiles_of(h) / 2); a.out_stats = h->fw.ce_stats; a.out_width = r.N;
         a.ntiles = tpp; a.tiles_per_pass = tpp; a.nrows = B;
         if (r.N > 32) { launch_lin(r.N, IN_FRAG, OUT_FRAG, false, a, s); continue; }
         FusedOp f;
@@ -1482,7 +1486,7 @@ int check_bound(const dsg_handle* h) {
 // ------------------------------------------------------------------------------------------------------
 int ensure_train_workspace(dsg_handle* h, int rows, int T) {
     if (ensure_workspace(h, rows, T)) return 1;
-    if (h->tr_ws && rows <= h->tr_rows && T == h->tr_T) return 0;
+    if (h->tr.ws && rows <= h->tr_rows && T == h->tr_T) return 0;
     HIPCK(hipDeviceSynchronize());
     const int nrows = rows > h->tr_rows ? rows : h->tr_rows;
     free_train_workspace(h);
@@ -1494,18 +1498,18 @@ int ensure_train_workspace(dsg_handle* h, int rows, int T) {
     for (auto& r : h->res) { r.dtb_off = so; so += (long long)r.N * T; }
     h->slab_stride = (size_t)((so + 63) / 64 * 64);
     const int max_chunks = 32;
-    HIPCK(hipMalloc(&h->tr_ws, tiles * h->tr_per_tile * sizeof(float)));
-    HIPCK(hipMemset(h->tr_ws, 0, tiles * h->tr_per_tile * sizeof(float)));
-    HIPCK(hipMalloc(&h->tr_slabs, (size_t)max_chunks * h->slab_stride * sizeof(float)));
+    HIPCK(h->tr.ws.alloc(tiles * h->tr_per_tile));
+    HIPCK(hipMemset(h->tr.ws, 0, tiles * h->tr_per_tile * sizeof(float)));
+    HIPCK(h->tr.slabs.alloc((size_t)max_chunks * h->slab_stride));
     // INVARIANT (AttentionBlock): the slab entries of attn.norm.* and of rows 0:2d of attn.projection.* are written by NOTHING after this
     // memset -- no weight-gradient unit, column sum or one-hot unit has an out_off inside them -- so the fixed-order reduce stores exact
     // zeros for them into the caller's bucket on every step.  Whoever adds a writer to those ranges must zero them per step instead.
-    HIPCK(hipMemset(h->tr_slabs, 0, (size_t)max_chunks * h->slab_stride * sizeof(float)));
-    HIPCK(hipMalloc(&h->tr_gsum, h->slab_stride * sizeof(float)));
+    HIPCK(hipMemset(h->tr.slabs, 0, (size_t)max_chunks * h->slab_stride * sizeof(float)));
+    HIPCK(h->tr.gsum.alloc(h->slab_stride));
     // + one set per early weight-gradient part + the complete set of the step's tail (the blocks' slots AND the Linears')
-    HIPCK(hipMalloc(&h->tr_gmax, (size_t)(2 + kMaxWgParts) * kMaxGmax * sizeof(unsigned)));
+    HIPCK(h->tr.gmax.alloc((size_t)(2 + kMaxWgParts) * kMaxGmax));
     h->gmax_ld = (int)tiles;
-    HIPCK(hipMalloc(&h->tr_gmax_t, (size_t)kMaxGmax * h->gmax_ld * sizeof(unsigned)));
+    HIPCK(h->tr.gmax_t.alloc((size_t)kMaxGmax * h->gmax_ld));
     {   // per-tile column sums of the residual blocks, one contiguous [tile][slot] region per block:
         // [dout | dh2 | dh1 | beta3 | gamma3 | beta2 | gamma2] x NP, [beta1 | gamma1] x KP
         const Param* P = h->params.data();
@@ -1542,13 +1546,13 @@ int ensure_train_workspace(dsg_handle* h, int rows, int T) {
         }
         if (off >= ((size_t)1 << 31)) { fail("training batch too large for the column-sum index (%zu floats)", off); return 1; }
         h->cs_slots = (int)map.size();
-        HIPCK(hipMalloc(&h->tr_cs, off * sizeof(float)));
-        HIPCK(hipMalloc(&h->cs_map_dev, map.size() * sizeof(int4)));
-        HIPCK(hipMemcpy(h->cs_map_dev, map.data(), map.size() * sizeof(int4), hipMemcpyHostToDevice));
+        HIPCK(h->tr.cs.alloc(off));
+        HIPCK(h->tr.cs_map_dev.alloc(map.size()));
+        HIPCK(hipMemcpy(h->tr.cs_map_dev, map.data(), map.size() * sizeof(int4), hipMemcpyHostToDevice));
     }
-    HIPCK(hipMalloc(&h->tr_ts, (size_t)nrows * sizeof(int)));
-    HIPCK(hipMalloc(&h->tr_yt_rm, (size_t)nrows * D * sizeof(float)));
-    HIPCK(hipMalloc(&h->tr_tsave, ((size_t)T * 2 * half + (size_t)(5 + kTimeChunks) * T * td) * sizeof(float)));
+    HIPCK(h->tr.ts.alloc((size_t)nrows));
+    HIPCK(h->tr.yt_rm.alloc((size_t)nrows * D));
+    HIPCK(h->tr.tsave.alloc((size_t)T * 2 * half + (size_t)(5 + kTimeChunks) * T * td));
     return 0;
 }
 
@@ -1569,7 +1573,7 @@ void fill_res_bwd_args(const dsg_handle* h, const Op& op, int tiles, BlockBwdArg
     a.gin0 = trp(h, h->tensors[op.in0].ga);
     a.gin1 = op.in1 >= 0 ? trp(h, h->tensors[op.in1].gb) : nullptr;
     a.du1 = trp(h, r.du1); a.dh1 = trp(h, r.dh1); a.dh2 = trp(h, r.dh2);
-    a.cs = h->tr_cs + r.cs_off; a.cs_stride = r.cs_stride;
+    a.cs = h->tr.cs + r.cs_off; a.cs_stride = r.cs_stride;
     a.rs1 = trp(h, r.rs1); a.rs2 = trp(h, r.rs2); a.rs3 = trp(h, r.rs3);
     a.ntiles = tiles;
     ah.b = a;
@@ -1578,7 +1582,7 @@ void fill_res_bwd_args(const dsg_handle* h, const Op& op, int tiles, BlockBwdArg
     ah.WscTh = r.sclin ? reinterpret_cast<const uint4*>(A + r.WscTh) : nullptr;
     ah.m1 = h->maxabs + r.l1.w; ah.m2 = h->maxabs + r.l2.w; ah.m3 = h->maxabs + r.l3.w;
     ah.msc = r.sclin ? h->maxabs + r.sc.w : nullptr;
-    ah.gmax_t = h->tr_gmax_t; ah.gmax_ld = h->gmax_ld; ah.slot_out = r.gslot_out; ah.slot_h2 = r.gslot_h2; ah.slot_h1 = r.gslot_h1;
+    ah.gmax_t = h->tr.gmax_t; ah.gmax_ld = h->gmax_ld; ah.slot_out = r.gslot_out; ah.slot_h2 = r.gslot_h2; ah.slot_h1 = r.gslot_h1;
 }
 void fill_lin_bwd_args(const dsg_handle* h, const Op& op, int tiles, LinBwdArgs& a) {
     const float* A = h->arena;
@@ -1601,7 +1605,7 @@ void fill_lin_bwd_args(const dsg_handle* h, const Op& op, int tiles, LinBwdArgs&
 int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
     // Rebuilding and uploading the tables costs four pageable host-to-device copies and a stream synchronise - a pipeline
     // drain in front of every step (the enqueue of a step's ~85 launches then no longer hides behind the previous step)
-    const void* key[6] = {h->tr_ws, h->ws, h->arena, h->cembed, h->condfrag, h->tb};
+    const void* key[6] = {h->tr.ws, h->fw.ws, h->arena, h->fw.cembed, h->fw.condfrag, h->fw.tb};
     if (h->td_valid && h->td_B == B && h->td_T == T && h->td_rows == h->tr_rows && h->td_split == h->use_split &&
         memcmp(key, h->td_key, sizeof key) == 0)
         return 0;
@@ -1654,7 +1658,7 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
         WgradDesc d;
         memset(&d, 0, sizeof d);
         d.G0 = G0; d.G1 = G1; d.N = N; d.NG = groups_of(N); d.amode = amode; d.a0 = a0; d.a1 = a1; d.rs = rs; d.gamma = gm; d.beta = bt;
-        d.ts = h->tr_ts; d.onehot_n = T; d.out_off = out_off; d.ld = ld;
+        d.ts = h->tr.ts; d.onehot_n = T; d.out_off = out_off; d.ld = ld;
         d.KG = amode == A_ONEHOT ? groups_of(T) : a0.groups + a1.groups;
         d.nrows = B;
         d.gmax_slot = slot_of(G0);
@@ -1697,7 +1701,7 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
             wgrad(dh1, nullptr, r.N, A_LNSILU, in0, in1, trp(h, r.rs1), A + r.g1p, A + r.b1p, P[r.l1.w].off, in);
             if (r.sclin) wgrad(ga, gb, r.N, A_RAW, in0, in1, nullptr, nullptr, nullptr, P[r.sc.w].off, in);
             wgrad(dh2, nullptr, r.N, A_LNSILU, gseg(trp(h, r.h1), r.N), none(), trp(h, r.rs2), A + r.g2p, A + r.b2p, P[r.l2.w].off, r.N);
-            wgrad(dh2, nullptr, r.N, A_RAW, gseg(h->condfrag, h->d.cond_dim), none(), nullptr, nullptr, nullptr, P[r.ce.w].off, h->d.cond_dim);
+            wgrad(dh2, nullptr, r.N, A_RAW, gseg(h->fw.condfrag, h->d.cond_dim), none(), nullptr, nullptr, nullptr, P[r.ce.w].off, h->d.cond_dim);
             wgrad(ga, gb, r.N, A_LNSILU, gseg(trp(h, r.h2), r.N), none(), trp(h, r.rs3), A + r.g3p, A + r.b3p, P[r.l3.w].off, r.N);
             wgrad(dh1, nullptr, r.N, A_ONEHOT, none(), none(), nullptr, nullptr, nullptr, r.dtb_off, T);
             // bias and LayerNorm gradients of the block come from the backward kernel's own column sums (k_cs_reduce); so does
@@ -1803,7 +1807,7 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
     }
     h->fbwd_n = (int)fb.size();
     if (h->fbwd_n) {
-        if (!h->fbwd_dev) HIPCK(hipMalloc(&h->fbwd_dev, (h->ops.size() + 1) * sizeof(FusedBwdOpH)));
+        if (!h->fbwd_dev) HIPCK(h->fbwd_dev.alloc(h->ops.size() + 1));
         HIPCK(hipMemcpyAsync(h->fbwd_dev, fb.data(), fb.size() * sizeof(FusedBwdOpH), hipMemcpyHostToDevice, s));
     }
     std::vector<ColsumUnit> cu;
@@ -1811,23 +1815,17 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
     for (size_t i = 0; i < cd.size(); ++i)
         for (int c = 0; c < h->tr_chunks; ++c)
             for (int g = 0; g < cd[i].groups; ++g) cu.push_back(ColsumUnit{(int)i, g, c, 0});
-    if (!h->wg_desc_dev) {
-        HIPCK(hipMalloc(&h->wg_desc_dev, wd.size() * sizeof(WgradDesc)));
-        HIPCK(hipMalloc(&h->cs_desc_dev, cd.size() * sizeof(ColsumDesc)));
+    if (!h->tr.wg_desc_dev) {
+        HIPCK(h->tr.wg_desc_dev.alloc(wd.size()));
+        HIPCK(h->tr.cs_desc_dev.alloc(cd.size()));
     }
-    if (h->wg_units != (int)wu.size() || !h->wg_unit_dev) {
-        if (h->wg_unit_dev) (void)hipFree(h->wg_unit_dev);
-        HIPCK(hipMalloc(&h->wg_unit_dev, wu.size() * sizeof(WgradUnit)));
-    }
-    if (h->cs_units != (int)cu.size() || !h->cs_unit_dev) {
-        if (h->cs_unit_dev) (void)hipFree(h->cs_unit_dev);
-        HIPCK(hipMalloc(&h->cs_unit_dev, cu.size() * sizeof(ColsumUnit)));
-    }
+    if (h->wg_units != (int)wu.size() || !h->tr.wg_unit_dev) HIPCK(h->tr.wg_unit_dev.alloc(wu.size()));   // (alloc frees the old table first)
+    if (h->cs_units != (int)cu.size() || !h->tr.cs_unit_dev) HIPCK(h->tr.cs_unit_dev.alloc(cu.size()));
     h->wg_units = (int)wu.size(); h->cs_units = (int)cu.size();
-    HIPCK(hipMemcpyAsync(h->wg_desc_dev, wd.data(), wd.size() * sizeof(WgradDesc), hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(h->cs_desc_dev, cd.data(), cd.size() * sizeof(ColsumDesc), hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(h->wg_unit_dev, wu.data(), wu.size() * sizeof(WgradUnit), hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(h->cs_unit_dev, cu.data(), cu.size() * sizeof(ColsumUnit), hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(h->tr.wg_desc_dev, wd.data(), wd.size() * sizeof(WgradDesc), hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(h->tr.cs_desc_dev, cd.data(), cd.size() * sizeof(ColsumDesc), hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(h->tr.wg_unit_dev, wu.data(), wu.size() * sizeof(WgradUnit), hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(h->tr.cs_unit_dev, cu.data(), cu.size() * sizeof(ColsumUnit), hipMemcpyHostToDevice, s));
     HIPCK(hipStreamSynchronize(s));  // host vectors go out of scope
     memcpy(h->td_key, key, sizeof key);
     if (!h->r2_dev) {   // the ranges of the flat gradient that the slabs hold: everything but what the time path produces (dsg_train_step);
@@ -1858,7 +1856,7 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
             for (long long v : starts) tab.push_back(v / 4);
             for (long long v : prefix) tab.push_back(v / 4);
         }
-        HIPCK(hipMalloc(&h->r2_dev, tab.size() * sizeof(long long)));
+        HIPCK(h->r2_dev.alloc(tab.size()));
         HIPCK(hipMemcpy(h->r2_dev, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice));
     }
     h->td_B = B; h->td_T = T; h->td_rows = h->tr_rows; h->td_split = h->use_split; h->td_valid = true;
@@ -2042,27 +2040,27 @@ static dsg_handle* create_impl(const dsg_unet_desc* desc, const int* is_attn, in
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             h->num_cus = cus;
     }
-    bool ok = hipMalloc(&h->ce_dev, (h->res.size() + 1) * sizeof(FusedOp)) == hipSuccess &&
-              hipMalloc(&h->fusedh_dev, (h->ops.size() + 1) * sizeof(FusedOpH)) == hipSuccess &&
-              hipMalloc(&h->tileops_dev, (h->ops.size() + 1) * sizeof(FusedOpH)) == hipSuccess &&
-              hipMalloc(&h->maxabs, (h->params.size() + 1) * sizeof(float)) == hipSuccess &&
-              hipMalloc(&h->fused_dev, 2 * (h->ops.size() + 1) * sizeof(FusedOp)) == hipSuccess &&
-              hipMalloc(&h->arena, h->arena_floats * sizeof(float)) == hipSuccess &&
+    bool ok = h->ce_dev.alloc(h->res.size() + 1) == hipSuccess &&
+              h->fusedh_dev.alloc(h->ops.size() + 1) == hipSuccess &&
+              h->tileops_dev.alloc(h->ops.size() + 1) == hipSuccess &&
+              h->maxabs.alloc(h->params.size() + 1) == hipSuccess &&
+              h->fused_dev.alloc(2 * (h->ops.size() + 1)) == hipSuccess &&
+              h->arena.alloc(h->arena_floats) == hipSuccess &&
               hipMemset(h->arena, 0, h->arena_floats * sizeof(float)) == hipSuccess &&
-              hipMalloc(&h->tdesc_dev, h->res.size() * sizeof(TimeBlockDesc)) == hipSuccess &&
-              hipMalloc(&h->freq, (d.proj_dim / 2) * sizeof(float)) == hipSuccess &&
-              hipMalloc(&h->red, 2 * kRedBlocks * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->step_dev, 128) == hipSuccess &&
+              h->tdesc_dev.alloc(h->res.size()) == hipSuccess &&
+              h->freq.alloc(d.proj_dim / 2) == hipSuccess &&
+              h->red.alloc(2 * kRedBlocks) == hipSuccess &&
+              h->step_dev.alloc(32) == hipSuccess &&
               hipMemset(h->step_dev, 0, 128) == hipSuccess &&
-              hipMalloc(&h->call_dev, sizeof(CallParams)) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) == hipSuccess;
+              h->call_dev.alloc(1) == hipSuccess &&
+              hipStreamCreateWithFlags(h->cap_stream.put(), hipStreamNonBlocking) == hipSuccess;
     if (ok) h->range_flag = h->step_dev + 16;      // its own 64-byte line of the same small allocation
     if (ok) {
         std::vector<OpConstDesc> oc;
         for (const ResP& r : h->res) oc.push_back(OpConstDesc{r.l1.w, r.l2.w, r.l3.w, r.sclin ? r.sc.w : -1});
         for (const LinOpP& l : h->lin) oc.push_back(OpConstDesc{l.l.w, -1, -1, -1});
-        ok = hipMalloc(&h->opc_desc_dev, oc.size() * sizeof(OpConstDesc)) == hipSuccess &&
-             hipMalloc(&h->opc_dev, oc.size() * 4 * sizeof(float)) == hipSuccess &&
+        ok = h->opc_desc_dev.alloc(oc.size()) == hipSuccess &&
+             h->opc_dev.alloc(oc.size() * 4) == hipSuccess &&
              hipMemcpy(h->opc_desc_dev, oc.data(), oc.size() * sizeof(OpConstDesc), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (ok) {
@@ -2073,7 +2071,7 @@ static dsg_handle* create_impl(const dsg_unet_desc* desc, const int* is_attn, in
         for (int k = 0; k < half; ++k) f[k] = expf((float)k * c);
         ok = hipMemcpy(h->freq, f.data(), half * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (!ok) { fail("device allocation failed in dsg_create"); dsg_destroy(h); return nullptr; }
+    if (!ok) { fail("device allocation failed in dsg_create"); delete h; return nullptr; }
     return h;
 }
 
@@ -2085,30 +2083,8 @@ dsg_handle* dsg_create_attn(const dsg_unet_desc* desc, const int* is_attn, int m
 }
 
 void dsg_destroy(dsg_handle* h) {
-    if (h && h->nlds_ops_dev) (void)hipFree(h->nlds_ops_dev);
-    if (h && h->nlds_copies_dev) (void)hipFree(h->nlds_copies_dev);
-    if (h && h->nlds_image) (void)hipFree(h->nlds_image);
-    if (h && h->v8_image) (void)hipFree(h->v8_image);
-    if (h && h->v8_copies_dev) (void)hipFree(h->v8_copies_dev);
-    if (h && h->seeds_dev) (void)hipFree(h->seeds_dev);
-    if (h && h->red_chunks) (void)hipFree(h->red_chunks);
-    if (h)
-        for (auto& e : h->tev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (!h) return;
     (void)hipDeviceSynchronize();
-    free_workspace(h);
-    void* ptrs[] = {h->arena, h->tdesc_dev, h->pack_dev, h->freq, h->red, h->step_dev, h->call_dev, h->fused_dev, h->maxabs,
-                    (void*)h->mx_ptrs_dev, h->mx_numel_dev, h->mx_idx_dev, h->packh_dev, h->opc_desc_dev, h->opc_dev, h->fusedh_dev, h->tileops_dev, h->fusedh_train_dev, h->tw_dst_dev, (void*)h->tw_src_dev, h->r2_dev, h->ce_dev, h->ctile_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->fbwd_dev) (void)hipFree(h->fbwd_dev);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (auto& e : h->ev_tail) if (e) (void)hipEventDestroy(e);
-    if (h->range_pinned) (void)hipHostFree(h->range_pinned);
     delete h;
 }
 
@@ -2158,8 +2134,8 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
             take(P[lu.l.w].ptr, 32); take(P[lu.l.b].ptr, 4);
             if (used != sec_u4) return fail("internal: float32 section image is %u uint4, expected %u", used, sec_u4);
             if (!h->v8_image) {
-                HIPCK(hipMalloc(&h->v8_image, (size_t)sec_u4 * sizeof(uint4)));
-                HIPCK(hipMalloc(&h->v8_copies_dev, cp.size() * sizeof(NarrowLdsCopy)));
+                HIPCK(h->v8_image.alloc((size_t)sec_u4 * 4));
+                HIPCK(h->v8_copies_dev.alloc(cp.size()));
             }
             HIPCK(hipMemcpy(h->v8_copies_dev, cp.data(), cp.size() * sizeof(NarrowLdsCopy), hipMemcpyHostToDevice));
             h->v8_ncopies = (int)cp.size();
@@ -2281,10 +2257,10 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
             h->mx_n = (int)mp.size(); h->packh_n = (int)hd.size(); h->packh_blocks = hb;
             if (h->mx_n) {
                 if (!h->mx_ptrs_dev) {
-                    HIPCK(hipMalloc(&h->mx_ptrs_dev, mp.size() * sizeof(float*)));
-                    HIPCK(hipMalloc(&h->mx_numel_dev, mn.size() * sizeof(long long)));
-                    HIPCK(hipMalloc(&h->packh_dev, hd.size() * sizeof(PackHDesc)));
-                    HIPCK(hipMalloc(&h->mx_idx_dev, mp.size() * sizeof(int)));
+                    HIPCK(h->mx_ptrs_dev.alloc(mp.size()));
+                    HIPCK(h->mx_numel_dev.alloc(mn.size()));
+                    HIPCK(h->packh_dev.alloc(hd.size()));
+                    HIPCK(h->mx_idx_dev.alloc(mp.size()));
                 }
                 HIPCK(hipMemcpy(h->mx_idx_dev, h->mx_param.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
                 HIPCK(hipMemcpy(h->mx_ptrs_dev, mp.data(), mp.size() * sizeof(float*), hipMemcpyHostToDevice));
@@ -2298,13 +2274,13 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
                 for (int n = 0; n < r.N; ++n) { dst.push_back(P[r.te.w].off + (long long)n * h->td); src.push_back(P[r.te.w].ptr + (size_t)n * h->td); }
             h->tw_rows = (int)dst.size();
             if (!h->tw_dst_dev) {
-                HIPCK(hipMalloc(&h->tw_dst_dev, dst.size() * sizeof(long long)));
-                HIPCK(hipMalloc(&h->tw_src_dev, src.size() * sizeof(float*)));
+                HIPCK(h->tw_dst_dev.alloc(dst.size()));
+                HIPCK(h->tw_src_dev.alloc(src.size()));
             }
             HIPCK(hipMemcpy(h->tw_dst_dev, dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice));
             HIPCK(hipMemcpy(h->tw_src_dev, src.data(), src.size() * sizeof(float*), hipMemcpyHostToDevice));
         }
-        if (!h->pack_dev) HIPCK(hipMalloc(&h->pack_dev, pd.size() * sizeof(PackDesc)));
+        if (!h->pack_dev) HIPCK(h->pack_dev.alloc(pd.size()));
         h->pack_n = (int)pd.size();
         h->pack_blocks = blk;
         HIPCK(hipMemcpyAsync(h->pack_dev, pd.data(), pd.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s));
@@ -2328,7 +2304,7 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
     // EMA swap would run the narrow run on the previous weights while every other block uses the new ones
     if (h->v8_ncopies > 0)      // first: the LDS image below takes the section from this buffer
         hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)h->v8_ncopies), dim3(64), 0, s, (const NarrowLdsCopy*)h->v8_copies_dev,
-                           reinterpret_cast<uint4*>(h->v8_image));
+                           reinterpret_cast<uint4*>(h->v8_image.get()));
     if (h->nlds_image && h->nlds_ncopies > 0)
         hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)h->nlds_ncopies), dim3(256), 0, s, (const NarrowLdsCopy*)h->nlds_copies_dev, h->nlds_image);
     HIPCK(hipGetLastError());
@@ -2410,8 +2386,8 @@ int dsg_range_status_stream(dsg_handle* h, int* exceeded, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     // Read AND clear in one step, on `s`: a one-thread kernel exchanges the flag with 0 and writes what it found into a pinned word (ADVICE r5:
     // "copy, then memset" lost a flag raised between the two by kernels of another stream -- twin handles, the side stream).  The pinned word
-    // belongs to the handle (freed in dsg_destroy); the copy is truly asynchronous and only `s` is waited for.
-    if (!h->range_pinned) HIPCK(hipHostMalloc(reinterpret_cast<void**>(&h->range_pinned), sizeof(int), hipHostMallocDefault));
+    // belongs to the handle; the copy is truly asynchronous and only `s` is waited for.
+    if (!h->range_pinned) HIPCK(h->range_pinned.alloc(1));
     hipLaunchKernelGGL(k_flag_take, dim3(1), dim3(64), 0, s, h->range_flag, h->range_pinned);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(s));
@@ -2444,15 +2420,15 @@ int dsg_unet_forward(dsg_handle* h, const float* x, const float* t, const float*
     if (B < 1) return fail("B must be >= 1");
     if (ensure_workspace(h, B, B)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    HIPCK(hipMemcpyAsync(h->tvals, t, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCK(hipMemcpyAsync(h->fw.tvals, t, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     run_time_path(h, B, s);
     const int tpp = cdiv(B, 32), CG = groups_of(h->d.cond_dim);
     hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tpp * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, h->d.cond_dim, CG,
-                       h->condfrag, tpp);
+                       h->fw.condfrag, tpp);
     // the handle's precision mode applies here as in dsg_sample / dsg_train_step: the split kernels take the condition embedding
     // Wc silu(cond * mask) precomputed (a masked row contributes exactly 0), the exact-f32 kernels compute it in the block
     if (h->use_split) run_cond_embed(h, B, s);
-    RunCtx c{B, 1, 0, x, out, nullptr, h->ts_ident, false, h->use_split};
+    RunCtx c{B, 1, 0, x, out, nullptr, h->fw.ts_ident, false, h->use_split};
     if (prepare_fused(h, c, s)) return 1;
     run_unet(h, c, s);
     HIPCK(hipGetLastError());
@@ -2463,7 +2439,7 @@ int dsg_unet_forward(dsg_handle* h, const float* x, const float* t, const float*
 // (a rank whose graphs are already cached would not issue it: the all-reduces would pair up wrongly or hang) and the caller's
 // `renorm_stats` pointer would be baked into the cached graph and outlive the hook.
 static int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, bool renorm, hipStream_t s,
-                        hipEvent_t* ev = nullptr, bool use_hook = true, int chunks = 1, size_t chunk_n = 0) {
+                        const Event* ev = nullptr, bool use_hook = true, int chunks = 1, size_t chunk_n = 0) {
     if (ev) {  // DSG_SAMPLE_PROFILE: one event pair per operator launch
         const bool fuse = h->fuse_hi - h->fuse_lo >= 2;
         bool skip_next = false;
@@ -2515,14 +2491,6 @@ static int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, boo
     return 0;
 }
 
-int dsg_sample_rec(dsg_handle* h, const float* cond, const float* y_T, const float* noise, unsigned long long seed, float omega,
-                   const float* coef, int T, float* out, int B, int flags, float* rec_y, float* rec_eps, void* stream);
-
-int dsg_sample(dsg_handle* h, const float* cond, const float* y_T, const float* noise, unsigned long long seed, float omega,
-               const float* coef, int T, float* out, int B, int flags, void* stream) {
-    return dsg_sample_rec(h, cond, y_T, noise, seed, omega, coef, T, out, B, flags, nullptr, nullptr, stream);
-}
-
 namespace {
 constexpr int kStepRunGraphs = 6;       // captured runs of 1, 2, 4, 8, 16, 32 later steps (dsg_handle::gexec)
 
@@ -2544,14 +2512,12 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     if (chunks > 1) {
         if (chunks > h->seeds_cap) {
             HIPCK(hipStreamSynchronize(s));
-            if (h->seeds_dev) (void)hipFree(h->seeds_dev);
-            HIPCK(hipMalloc(&h->seeds_dev, (size_t)chunks * sizeof(unsigned long long)));
+            HIPCK(h->seeds_dev.alloc((size_t)chunks));
             h->seeds_cap = chunks;
         }
         if (chunks > h->red_chunks_cap) {
             HIPCK(hipStreamSynchronize(s));
-            if (h->red_chunks) (void)hipFree(h->red_chunks);
-            HIPCK(hipMalloc(&h->red_chunks, (size_t)2 * chunks * kRedBlocks * sizeof(double)));
+            HIPCK(h->red_chunks.alloc((size_t)2 * chunks * kRedBlocks));
             h->red_chunks_cap = chunks;
             free_graphs(h);                        // the captured renorm kernels hold the old buffer
         }
@@ -2562,38 +2528,36 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     }
 
     // per-call setup: time table for all T steps, condition fragments, start state, step counter
-    hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->tvals, T);
+    hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->fw.tvals, T);
     run_time_path(h, T, s);
     hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tpp * CG * 256, 256)), dim3(256), 0, s, cond, (const float*)nullptr, B,
-                       h->d.cond_dim, CG, h->condfrag, tpp);
+                       h->d.cond_dim, CG, h->fw.condfrag, tpp);
     // condition embeddings of every block, once per call: cond is the same in all T steps (MSR.py:126-127)
     run_cond_embed(h, B, s);
-    if (y_T) HIPCK(hipMemcpyAsync(h->ywork, y_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    else if (chunks > 1) hipLaunchKernelGGL(k_randn_chunked, dim3(2048), dim3(256), 0, s, h->ywork, n, (const unsigned long long*)h->seeds_dev, chunk_n / 4, 0xFFFFFFFFu);
-    else hipLaunchKernelGGL(k_randn, dim3(2048), dim3(256), 0, s, h->ywork, n, seed, 0xFFFFFFFFu);
+    if (y_T) HIPCK(hipMemcpyAsync(h->fw.ywork, y_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else if (chunks > 1) hipLaunchKernelGGL(k_randn_chunked, dim3(2048), dim3(256), 0, s, h->fw.ywork, n, (const unsigned long long*)h->seeds_dev, chunk_n / 4, 0xFFFFFFFFu);
+    else hipLaunchKernelGGL(k_randn, dim3(2048), dim3(256), 0, s, h->fw.ywork, n, seed, 0xFFFFFFFFu);
     // step counter (every step's first operator decrements it before anything reads it: step T-1 first) and the call block go
     // to the device as kernel arguments: no pageable copy, no synchronise - consecutive calls pipeline on the stream
     const CallParams cp{noise, coef, omega, T, seed, rec_y, rec_eps, chunk_n / 4, chunks > 1 ? h->seeds_dev : nullptr};
-    hipLaunchKernelGGL(k_set_call, dim3(1), dim3(64), 0, s, h->step_dev, reinterpret_cast<CallParams*>(h->call_dev), cp, T);
+    hipLaunchKernelGGL(k_set_call, dim3(1), dim3(64), 0, s, h->step_dev, h->call_dev.get(), cp, T);
 
-    RunCtx c{B, 2, tpp, h->ywork, h->eps, h->step_dev, nullptr, false, true};
+    RunCtx c{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true};
     c.advance_step = h->step_dev;
     c.share_proj = split_ctx(h, c);
     if (prepare_fused(h, c, s)) return 1;
     UpdateArgs u;
-    u.eps = h->eps; u.y = h->ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
+    u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
     const int n_renorm = T < 4 ? T : 4;  // steps i > T-5 (MSR.py:136)
     if (flags & DSG_SAMPLE_PROFILE) {
         const size_t nops = h->ops.size();
         h->op_ms.assign(nops, 0.0);
         h->op_calls.assign(nops, 0);
-        std::vector<hipEvent_t> ev(2 * nops);
-        for (auto& e : ev) HIPCK(hipEventCreate(&e));
-        int rc = 0;
-        for (int k = 0; k < T && !rc; ++k) rc = enqueue_step(h, c, u, k < n_renorm, s, ev.data(), true, chunks, chunk_n);
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        if (rc) return 1;
+        std::vector<Event> ev(2 * nops);
+        for (auto& e : ev) HIPCK(hipEventCreate(e.put()));
+        for (int k = 0; k < T; ++k)
+            if (enqueue_step(h, c, u, k < n_renorm, s, ev.data(), true, chunks, chunk_n)) return 1;
     } else if (flags & DSG_SAMPLE_NO_GRAPH) {
         for (int k = 0; k < T; ++k)
             if (enqueue_step(h, c, u, k < n_renorm, s, nullptr, true, chunks, chunk_n)) return 1;
@@ -2618,7 +2582,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
-            e = hipGraphInstantiate(&h->gexec[variant], g, nullptr, nullptr, 0);
+            e = hipGraphInstantiate(h->gexec[variant].put(), g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (e != hipSuccess) return fail("hipGraphInstantiate: %s", hipGetErrorString(e));
             return 0;
@@ -2639,7 +2603,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             left -= 1 << v;
         }
     }
-    HIPCK(hipMemcpyAsync(out, h->ywork, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCK(hipMemcpyAsync(out, h->fw.ywork, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 }  // namespace
@@ -2647,6 +2611,11 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
 int dsg_sample_rec(dsg_handle* h, const float* cond, const float* y_T, const float* noise, unsigned long long seed, float omega,
                    const float* coef, int T, float* out, int B, int flags, float* rec_y, float* rec_eps, void* stream) {
     return sample_impl(h, cond, y_T, noise, seed, nullptr, 0, omega, coef, T, out, B, flags, rec_y, rec_eps, (hipStream_t)stream);
+}
+
+int dsg_sample(dsg_handle* h, const float* cond, const float* y_T, const float* noise, unsigned long long seed, float omega,
+               const float* coef, int T, float* out, int B, int flags, void* stream) {
+    return dsg_sample_rec(h, cond, y_T, noise, seed, omega, coef, T, out, B, flags, nullptr, nullptr, stream);
 }
 
 int dsg_sample_chunked(dsg_handle* h, const float* cond, const float* y_T, const float* noise, const unsigned long long* seeds, int chunk_rows,
@@ -2659,72 +2628,14 @@ int dsg_sample_chunked(dsg_handle* h, const float* cond, const float* y_T, const
 // training step
 // ------------------------------------------------------------------------------------------------------
 namespace {
-int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
-                    const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, hipStream_t s);
-}
-
-int dsg_train_step(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
-                   const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, void* stream) {
-    if (check_bound(h)) return 1;
-    if (B < 1 || T < 1) return fail("B and T must be >= 1");
-    if (!y || !cond || !ts || !noise || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out)
-        return fail("dsg_train_step: null pointer argument");
-    if (ensure_train_workspace(h, B, T)) return 1;
-    return train_step_impl(h, y, cond, ts, noise, cond_mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
-}
-
-int dsg_train_draws(unsigned long long seed, unsigned long long call, int T, float keep_prob, int B, int D, int* ts, float* noise,
-                    float* cond_mask, void* stream) {
-    if (B < 1 || D < 1 || T < 1) return fail("dsg_train_draws: B, D and T must be >= 1");
-    if (call >> 30) return fail("dsg_train_draws: call counter out of range (2^30)");
-    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, (hipStream_t)stream, ts, noise, cond_mask, B, D, T, keep_prob, seed, (unsigned)call,
-                       (const unsigned long long*)nullptr);
-    HIPCK(hipGetLastError());
+// the device-side draws of the seeded steps ([rows][D] noise, [rows] mask): allocated on first use, dropped with the training workspace
+int ensure_train_draws(dsg_handle* h) {
+    if (h->tr.noise) return 0;
+    HIPCK(h->tr.noise.alloc((size_t)h->tr_rows * h->d.input_dim));
+    HIPCK(h->tr.mask.alloc((size_t)h->tr_rows));
     return 0;
 }
 
-int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, unsigned long long seed, unsigned long long* call_dev,
-                              float keep_prob, const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out,
-                              int B, void* stream) {
-    if (check_bound(h)) return 1;
-    if (B < 1 || T < 1) return fail("B and T must be >= 1");
-    if (!y || !cond || !call_dev || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded_dyn: null pointer argument");
-    if (ensure_train_workspace(h, B, T)) return 1;
-    const int D = h->d.input_dim;
-    if (!h->tr_noise) {
-        HIPCK(hipMalloc(&h->tr_noise, (size_t)h->tr_rows * D * sizeof(float)));
-        HIPCK(hipMalloc(&h->tr_mask, (size_t)h->tr_rows * sizeof(float)));
-    }
-    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, s, h->tr_ts, h->tr_noise, h->tr_mask, B, D, T, keep_prob, seed, 0u,
-                       (const unsigned long long*)call_dev);
-    hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(64), 0, s, call_dev);
-    HIPCK(hipGetLastError());
-    return train_step_impl(h, y, cond, h->tr_ts, h->tr_noise, h->tr_mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, s);
-}
-
-int dsg_train_step_seeded(dsg_handle* h, const float* y, const float* cond, unsigned long long seed, unsigned long long call,
-                          float keep_prob, const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out,
-                          int B, void* stream) {
-    if (check_bound(h)) return 1;
-    if (B < 1 || T < 1) return fail("B and T must be >= 1");
-    if (!y || !cond || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded: null pointer argument");
-    if (ensure_train_workspace(h, B, T)) return 1;
-    const int D = h->d.input_dim;
-    if (!h->tr_noise) {
-        HIPCK(hipMalloc(&h->tr_noise, (size_t)h->tr_rows * D * sizeof(float)));
-        HIPCK(hipMalloc(&h->tr_mask, (size_t)h->tr_rows * sizeof(float)));
-    }
-    // ts goes straight into the workspace copy the step reads (train_step_impl skips its own copy when handed that pointer)
-    if (dsg_train_draws(seed, call, T, keep_prob, B, D, h->tr_ts, h->tr_noise, h->tr_mask, stream)) return 1;
-    return train_step_impl(h, y, cond, h->tr_ts, h->tr_noise, h->tr_mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
-}
-
-namespace {
 int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
                     const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, hipStream_t s) {
     // every shape the backward kernels cannot take is refused HERE, before anything is enqueued (the same check in the middle of
@@ -2742,7 +2653,7 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     // ---- forward
     auto mark = [&](int i) { if (h->train_prof) (void)hipEventRecord(h->tev[i], s); };
     mark(0);
-    if (ts != h->tr_ts) HIPCK(hipMemcpyAsync(h->tr_ts, ts, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (ts != h->tr.ts) HIPCK(hipMemcpyAsync(h->tr.ts, ts, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
     // The time path forward (TimeEmbedding + the blocks' time_emb Linears over the T table rows: five short dependent launches) needs
     // nothing of the batch: once the side stream exists (large batches, from the second step on) it runs there, beside the draws'
     // consumers (condition fragments, q-sample, condition embeddings), and joins in front of the first block.
@@ -2752,34 +2663,34 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
         HIPCK(hipEventRecord(h->ev_tail[0], s));                           // the weights of this step (optimizer step, re-pack) are in place
         HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_tail[0], 0));
     }
-    hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, tstream, h->tvals, T);
+    hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, tstream, h->fw.tvals, T);
     run_time_path(h, T, tstream, true);
     if (time_fwd_beside) HIPCK(hipEventRecord(h->ev_tail[2], h->side_stream));
-    hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tiles * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, C, CG, h->condfrag, tiles);
-    hipLaunchKernelGGL(k_qsample, dim3(cdiv(tiles * DG * 256, 256)), dim3(256), 0, s, y, noise, h->tr_ts, sqrt_acp, sqrt_1m_acp, B, D,
-                       h->tr_yt_rm, trp(h, h->tr_yt_frag), tiles);
+    hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tiles * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, C, CG, h->fw.condfrag, tiles);
+    hipLaunchKernelGGL(k_qsample, dim3(cdiv(tiles * DG * 256, 256)), dim3(256), 0, s, y, noise, h->tr.ts, sqrt_acp, sqrt_1m_acp, B, D,
+                       h->tr.yt_rm, trp(h, h->tr_yt_frag), tiles);
     // the forward may run on the split-f16 kernels (they need the condition embeddings as an additive term)
     if (h->use_split) run_cond_embed(h, B, s);
-    RunCtx c{B, 1, 0, h->tr_yt_rm, h->eps, nullptr, h->tr_ts, true, h->use_split};
+    RunCtx c{B, 1, 0, h->tr.yt_rm, h->fw.eps, nullptr, h->tr.ts, true, h->use_split};
     if (prepare_fused(h, c, s)) return 1;
     if (time_fwd_beside) HIPCK(hipStreamWaitEvent(s, h->ev_tail[2], 0));   // the time table
     run_unet(h, c, s);
-    hipLaunchKernelGGL(k_loss_grad, dim3(kRedBlocks), dim3(256), 0, s, h->eps, noise, B, D, trp(h, h->tr_deps), tiles, h->red);
+    hipLaunchKernelGGL(k_loss_grad, dim3(kRedBlocks), dim3(256), 0, s, h->fw.eps, noise, B, D, trp(h, h->tr_deps), tiles, h->red);
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(256), 0, s, h->red, kRedBlocks, (double)B * (double)D, loss_out);
 
     // ---- backward: activation gradients in reverse operator order
     mark(1);
-    HIPCK(hipMemsetAsync(h->tr_gmax_t, 0, (size_t)h->n_gmax * h->gmax_ld * sizeof(unsigned), s));
+    HIPCK(hipMemsetAsync(h->tr.gmax_t, 0, (size_t)h->n_gmax * h->gmax_ld * sizeof(unsigned), s));
     int next_part = 0;
     if (h->use_split && !h->wg_fork_ops.empty() && !h->side_stream) {
-        HIPCK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        HIPCK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        HIPCK(hipStreamCreateWithFlags(h->side_stream.put(), hipStreamNonBlocking));
+        HIPCK(hipEventCreateWithFlags(h->ev_fork.put(), hipEventDisableTiming));
+        HIPCK(hipEventCreateWithFlags(h->ev_join.put(), hipEventDisableTiming));
         HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_h), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
         // (The step's tail runs on the side stream too, behind the early parts.  A separate high-priority stream for it measured 2 %
         // faster in a process of its own and 2.2x SLOWER -- 4.3 ms per step -- as soon as a second handle was alive in the process,
         // bench.py's sampling model: profiles/r04_train_tail_ab.txt.  No stream priorities.)
-        for (auto& e : h->ev_tail) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto& e : h->ev_tail) HIPCK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
     }
     // the G and A operands of a part are final once the backward kernel of its last block is enqueued: its weight gradients run
     // on the side stream from there, beside the remaining chain kernels (one wave per SIMD below 65 536 rows: latency-bound,
@@ -2787,13 +2698,13 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     auto fork_parts = [&](int done_op) -> int {
         while (next_part < (int)h->wg_fork_ops.size() && h->wg_fork_ops[next_part] >= done_op) {
             const int u0 = next_part ? h->wg_part_end[next_part - 1] : 0, u1 = h->wg_part_end[next_part];
-            unsigned* gm = h->tr_gmax + (size_t)(1 + next_part) * kMaxGmax;
+            unsigned* gm = h->tr.gmax + (size_t)(1 + next_part) * kMaxGmax;
             HIPCK(hipEventRecord(h->ev_fork, s));
             HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-            hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, h->side_stream, h->tr_gmax_t, h->gmax_ld, gm);
+            hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, h->side_stream, h->tr.gmax_t, h->gmax_ld, gm);
             if (u1 > u0)
-                hipLaunchKernelGGL(k_wgrad_h, dim3(u1 - u0), dim3(256), h->wg_early_lds, h->side_stream, h->wg_desc_dev, h->wg_unit_dev + u0,
-                                   gm, h->tr_slabs, h->slab_stride, tiles, h->tr_chunks);
+                hipLaunchKernelGGL(k_wgrad_h, dim3(u1 - u0), dim3(256), h->wg_early_lds, h->side_stream, h->tr.wg_desc_dev, h->tr.wg_unit_dev + u0,
+                                   gm, h->tr.slabs, h->slab_stride, tiles, h->tr_chunks);
             ++next_part;
         }
         return 0;
@@ -2840,30 +2751,30 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     mark(2);
     const bool time_beside = h->use_split && next_part > 0 && h->side_stream && h->opt_time_beside;
     hipStream_t cs_stream = time_beside ? h->side_stream : s;
-    unsigned* const gm_all = time_beside ? h->tr_gmax + (size_t)(1 + kMaxWgParts) * kMaxGmax : h->tr_gmax;
+    unsigned* const gm_all = time_beside ? h->tr.gmax + (size_t)(1 + kMaxWgParts) * kMaxGmax : h->tr.gmax;
     auto units = [&](int lo, int hi, const unsigned* gm, hipStream_t us) {
         if (hi > lo)
-            hipLaunchKernelGGL(k_wgrad_h, dim3(hi - lo), dim3(256), 0, us, h->wg_desc_dev, h->wg_unit_dev + lo, gm, h->tr_slabs, h->slab_stride,
+            hipLaunchKernelGGL(k_wgrad_h, dim3(hi - lo), dim3(256), 0, us, h->tr.wg_desc_dev, h->tr.wg_unit_dev + lo, gm, h->tr.slabs, h->slab_stride,
                                tiles, h->tr_chunks);
     };
     const int u0 = next_part ? h->wg_part_end[next_part - 1] : 0;
     if (time_beside) {
         // the blocks' slots are complete; the Linears' are not yet, and nothing reads them from this set
-        hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, s, h->tr_gmax_t, h->gmax_ld, h->tr_gmax);
+        hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, s, h->tr.gmax_t, h->gmax_ld, h->tr.gmax);
         HIPCK(hipEventRecord(h->ev_tail[0], s));
         HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_tail[0], 0));
-        units(u0, h->wg_onehot_end, h->tr_gmax, h->side_stream);
+        units(u0, h->wg_onehot_end, h->tr.gmax, h->side_stream);
     }
-    hipLaunchKernelGGL(k_cs_reduce, dim3(cdiv(h->cs_slots, 256), h->tr_chunks), dim3(256), 0, cs_stream, h->tr_cs, h->cs_map_dev, h->cs_slots,
-                       h->tr_slabs, h->slab_stride, tiles, h->tr_chunks);
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(h->cs_units, 4)), dim3(256), 0, cs_stream, h->cs_desc_dev, h->cs_unit_dev, h->cs_units, h->tr_slabs,
-                       h->slab_stride, tiles, h->tr_chunks, B, h->tr_gmax_t, h->gmax_ld);
-    hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, cs_stream, h->tr_gmax_t, h->gmax_ld, gm_all);
+    hipLaunchKernelGGL(k_cs_reduce, dim3(cdiv(h->cs_slots, 256), h->tr_chunks), dim3(256), 0, cs_stream, h->tr.cs, h->tr.cs_map_dev, h->cs_slots,
+                       h->tr.slabs, h->slab_stride, tiles, h->tr_chunks);
+    hipLaunchKernelGGL(k_colsum, dim3(cdiv(h->cs_units, 4)), dim3(256), 0, cs_stream, h->tr.cs_desc_dev, h->tr.cs_unit_dev, h->cs_units, h->tr.slabs,
+                       h->slab_stride, tiles, h->tr_chunks, B, h->tr.gmax_t, h->gmax_ld);
+    hipLaunchKernelGGL(k_gmax_reduce, dim3(h->n_gmax), dim3(256), 0, cs_stream, h->tr.gmax_t, h->gmax_ld, gm_all);
     mark(3);
     const size_t dtb0 = (size_t)h->total_params, dtb_n = h->slab_stride - dtb0;
     auto reduce_blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)); };
     auto time_path = [&](float* G, hipStream_t ts) {
-        float* emb = h->tr_tsave;
+        float* emb = h->tr.tsave;
         float* h1pre = emb + (size_t)T * 2 * half;
         float* h1s = h1pre + (size_t)T * td;
         float* tpre = h1s + (size_t)T * td;
@@ -2871,8 +2782,8 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
         float* d_h1s = d_st + (size_t)T * td;
         float* tpart = d_h1s + (size_t)T * td;   // [kTimeChunks][T][td]
         // all blocks at once: their dTB rows are contiguous from the first block's dtb_off
-        const float* dtb_all = h->tr_gsum + h->res[0].dtb_off;
-        hipLaunchKernelGGL(k_time_wgrad, dim3(2048), dim3(256), 0, ts, dtb_all, T, h->st, td, h->tw_dst_dev, G, h->tw_rows);
+        const float* dtb_all = h->tr.gsum + h->res[0].dtb_off;
+        hipLaunchKernelGGL(k_time_wgrad, dim3(2048), dim3(256), 0, ts, dtb_all, T, h->fw.st, td, h->tw_dst_dev, G, h->tw_rows);
         hipLaunchKernelGGL(k_time_dgrad, dim3(cdiv(T * td, 256), kTimeChunks), dim3(256), 0, ts, dtb_all, T, h->tw_src_dev, td, tpart, h->tw_rows);
         const unsigned eb = (unsigned)cdiv(T * td, 256);
         hipLaunchKernelGGL(k_time_dgrad_finish, dim3(eb), dim3(256), 0, ts, tpart, tpre, d_st, (size_t)T * td);  // d temb (pre-Swish)
@@ -2884,36 +2795,36 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
         hipLaunchKernelGGL(k_col_sum_small, dim3(cdiv(td, 256)), dim3(256), 0, ts, d_h1s, T, td, (long long)td, G + P[h->temb_l1b].off);
     };
     if (time_beside) {
-        units(h->wg_onehot_end, h->wg_blocks_end, h->tr_gmax, s);
+        units(h->wg_onehot_end, h->wg_blocks_end, h->tr.gmax, s);
         HIPCK(hipEventRecord(h->ev_tail[2], h->side_stream));              // column sums done: the Linears' scales
         HIPCK(hipStreamWaitEvent(s, h->ev_tail[2], 0));
         units(h->wg_blocks_end, h->wg_units, gm_all, s);
-        hipLaunchKernelGGL(k_reduce_slabs, reduce_blocks(dtb_n), dim3(256), 0, h->side_stream, h->tr_slabs + dtb0, h->slab_stride, h->tr_chunks,
-                           h->tr_gsum + dtb0, dtb_n);
+        hipLaunchKernelGGL(k_reduce_slabs, reduce_blocks(dtb_n), dim3(256), 0, h->side_stream, h->tr.slabs + dtb0, h->slab_stride, h->tr_chunks,
+                           h->tr.gsum + dtb0, dtb_n);
         time_path(grads_flat, h->side_stream);       // straight into the caller's bucket: the last reduce leaves these regions out
         HIPCK(hipEventRecord(h->ev_tail[1], h->side_stream));
         HIPCK(hipStreamWaitEvent(s, h->ev_tail[1], 0));
         mark(4);
         if (h->r2_vec4 && (reinterpret_cast<unsigned long long>(grads_flat) & 15ull) == 0)
-            hipLaunchKernelGGL(k_reduce_ranges4, reduce_blocks((size_t)h->r2_total / 4), dim3(256), 0, s, h->tr_slabs, h->slab_stride, h->tr_chunks,
+            hipLaunchKernelGGL(k_reduce_ranges4, reduce_blocks((size_t)h->r2_total / 4), dim3(256), 0, s, h->tr.slabs, h->slab_stride, h->tr_chunks,
                                grads_flat, (const long long*)(h->r2_dev + 2 * h->r2_n), (const long long*)(h->r2_dev + 3 * h->r2_n), h->r2_n,
                                h->r2_total / 4);
         else
-            hipLaunchKernelGGL(k_reduce_ranges, reduce_blocks((size_t)h->r2_total), dim3(256), 0, s, h->tr_slabs, h->slab_stride, h->tr_chunks,
+            hipLaunchKernelGGL(k_reduce_ranges, reduce_blocks((size_t)h->r2_total), dim3(256), 0, s, h->tr.slabs, h->slab_stride, h->tr_chunks,
                                grads_flat, (const long long*)h->r2_dev, (const long long*)(h->r2_dev + h->r2_n), h->r2_n, h->r2_total);
     } else {
         if (h->use_split) {
             if (next_part) HIPCK(hipEventRecord(h->ev_join, h->side_stream));
-            units(u0, h->wg_units, h->tr_gmax, s);
+            units(u0, h->wg_units, h->tr.gmax, s);
             if (next_part) HIPCK(hipStreamWaitEvent(s, h->ev_join, 0));
         } else
-            hipLaunchKernelGGL(k_wgrad, dim3(h->wg_units), dim3(256), 0, s, h->wg_desc_dev, h->wg_unit_dev, h->tr_slabs, h->slab_stride, tiles,
+            hipLaunchKernelGGL(k_wgrad, dim3(h->wg_units), dim3(256), 0, s, h->tr.wg_desc_dev, h->tr.wg_unit_dev, h->tr.slabs, h->slab_stride, tiles,
                                h->tr_chunks);
         mark(4);
-        hipLaunchKernelGGL(k_reduce_slabs, reduce_blocks(h->slab_stride), dim3(256), 0, s, h->tr_slabs, h->slab_stride, h->tr_chunks,
-                           h->tr_gsum, h->slab_stride);
-        time_path(h->tr_gsum, s);
-        HIPCK(hipMemcpyAsync(grads_flat, h->tr_gsum, (size_t)h->total_params * sizeof(float), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_reduce_slabs, reduce_blocks(h->slab_stride), dim3(256), 0, s, h->tr.slabs, h->slab_stride, h->tr_chunks,
+                           h->tr.gsum, h->slab_stride);
+        time_path(h->tr.gsum, s);
+        HIPCK(hipMemcpyAsync(grads_flat, h->tr.gsum, (size_t)h->total_params * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     mark(5);
     if (h->train_prof) h->tev_valid = true;
@@ -2922,10 +2833,65 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
 }
 }  // namespace
 
+int dsg_train_step(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
+                   const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, void* stream) {
+    if (check_bound(h)) return 1;
+    if (B < 1 || T < 1) return fail("B and T must be >= 1");
+    if (!y || !cond || !ts || !noise || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out)
+        return fail("dsg_train_step: null pointer argument");
+    if (ensure_train_workspace(h, B, T)) return 1;
+    return train_step_impl(h, y, cond, ts, noise, cond_mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
+}
+
+int dsg_train_draws(unsigned long long seed, unsigned long long call, int T, float keep_prob, int B, int D, int* ts, float* noise,
+                    float* cond_mask, void* stream) {
+    if (B < 1 || D < 1 || T < 1) return fail("dsg_train_draws: B, D and T must be >= 1");
+    if (call >> 30) return fail("dsg_train_draws: call counter out of range (2^30)");
+    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, (hipStream_t)stream, ts, noise, cond_mask, B, D, T, keep_prob, seed, (unsigned)call,
+                       (const unsigned long long*)nullptr);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, unsigned long long seed, unsigned long long* call_dev,
+                              float keep_prob, const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out,
+                              int B, void* stream) {
+    if (check_bound(h)) return 1;
+    if (B < 1 || T < 1) return fail("B and T must be >= 1");
+    if (!y || !cond || !call_dev || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded_dyn: null pointer argument");
+    if (ensure_train_workspace(h, B, T)) return 1;
+    const int D = h->d.input_dim;
+    if (ensure_train_draws(h)) return 1;
+    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, s, h->tr.ts, h->tr.noise, h->tr.mask, B, D, T, keep_prob, seed, 0u,
+                       (const unsigned long long*)call_dev);
+    hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(64), 0, s, call_dev);
+    HIPCK(hipGetLastError());
+    return train_step_impl(h, y, cond, h->tr.ts, h->tr.noise, h->tr.mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, s);
+}
+
+int dsg_train_step_seeded(dsg_handle* h, const float* y, const float* cond, unsigned long long seed, unsigned long long call,
+                          float keep_prob, const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out,
+                          int B, void* stream) {
+    if (check_bound(h)) return 1;
+    if (B < 1 || T < 1) return fail("B and T must be >= 1");
+    if (!y || !cond || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded: null pointer argument");
+    if (ensure_train_workspace(h, B, T)) return 1;
+    const int D = h->d.input_dim;
+    if (ensure_train_draws(h)) return 1;
+    // ts goes straight into the workspace copy the step reads (train_step_impl skips its own copy when handed that pointer)
+    if (dsg_train_draws(seed, call, T, keep_prob, B, D, h->tr.ts, h->tr.noise, h->tr.mask, stream)) return 1;
+    return train_step_impl(h, y, cond, h->tr.ts, h->tr.noise, h->tr.mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
+}
+
 int dsg_train_profile_enable(dsg_handle* h, int on) {
     if (!h) return fail("null handle");
     if (on && !h->tev[0])
-        for (auto& e : h->tev) HIPCK(hipEventCreate(&e));
+        for (auto& e : h->tev) HIPCK(hipEventCreate(e.put()));
     h->train_prof = on != 0;
     h->tev_valid = false;
     return 0;
@@ -2988,28 +2954,29 @@ int eval_args(const void* a, const void* b, long long rows, int D, const char* w
     if (!a || !b || rows < 0 || D < 1) return fail("%s: bad arguments", who);
     return 0;
 }
-// part[0] <- (min, max) of columns [c0, c1) of the whole tensor; stream-ordered scratch, freed by the caller after its consumer
-int minmax_global(const float* y, long long rows, int D, int c0, int c1, float2** part, hipStream_t s) {
+// part[0] <- (min, max) of columns [c0, c1) of the whole tensor; stream-ordered scratch, released when the caller's `part` goes out of
+// scope, behind its consumer
+int minmax_global(const float* y, long long rows, int D, int c0, int c1, StreamScratch<float2>& part, hipStream_t s) {
     const int w = c1 - c0, lpr = w >= 64 ? 64 : (w >= 16 ? 16 : (w >= 4 ? 4 : 1));
     const long long want = (rows + 4LL * (64 / lpr) - 1) / (4LL * (64 / lpr));   // one trip of k_minmax_partial per block if it fits
     const int nparts = (int)(want < kEvalParts ? want : kEvalParts);
-    HIPCK(hipMallocAsync(reinterpret_cast<void**>(part), (size_t)(1 + nparts) * sizeof(float2), s));
-    hipLaunchKernelGGL(k_minmax_partial, dim3(nparts), dim3(256), 0, s, y, rows, D, c0, c1, *part);
-    hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(256), 0, s, *part, nparts);
+    HIPCK(part.alloc((size_t)1 + nparts, s));
+    hipLaunchKernelGGL(k_minmax_partial, dim3(nparts), dim3(256), 0, s, y, rows, D, c0, c1, part.get());
+    hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(256), 0, s, part.get(), nparts);
     return 0;
 }
 template <int MODE>
 int softmax_rows(const float* y, float* out, long long rows, int D, hipStream_t s, int c0, int c1) {
     if (rows == 0) return 0;
-    float2* part = nullptr;
-    if (MODE == 1 && minmax_global(y, rows, D, c0, c1, &part, s)) return 1;
+    StreamScratch<float2> scratch;
+    if (MODE == 1 && minmax_global(y, rows, D, c0, c1, scratch, s)) return 1;
+    const float2* part = scratch;
     auto blocks = [&](int lpr) { const long long rpb = 4LL * (64 / lpr); return dim3((unsigned)((rows + rpb - 1) / rpb)); };
     if (D <= kSoftEpl) hipLaunchKernelGGL((k_row_softmax<MODE, 1>), blocks(1), dim3(256), 0, s, y, out, rows, D, part);
     else if (D <= 4 * kSoftEpl) hipLaunchKernelGGL((k_row_softmax<MODE, 4>), blocks(4), dim3(256), 0, s, y, out, rows, D, part);
     else if (D <= 16 * kSoftEpl) hipLaunchKernelGGL((k_row_softmax<MODE, 16>), blocks(16), dim3(256), 0, s, y, out, rows, D, part);
     else if (D <= 64 * kSoftEpl) hipLaunchKernelGGL((k_row_softmax<MODE, 64>), blocks(64), dim3(256), 0, s, y, out, rows, D, part);
     else hipLaunchKernelGGL((k_row_softmax_wide<MODE>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, y, out, rows, D, part);
-    if (part) HIPCK(hipFreeAsync(part, s));
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -3051,10 +3018,9 @@ int dsg_nu_decode(const float* y, float* out, long long rows, int D, float width
     if (D < 3) return fail("dsg_nu_decode: D = %d (two position columns and at least one power column)", D);
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    float2* part = nullptr;
-    if (minmax_global(y, rows, D, 0, 2, &part, s)) return 1;
-    hipLaunchKernelGGL(k_nu_decode, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, y, out, rows, D, width, height, p_sum, part);
-    HIPCK(hipFreeAsync(part, s));
+    StreamScratch<float2> part;
+    if (minmax_global(y, rows, D, 0, 2, part, s)) return 1;
+    hipLaunchKernelGGL(k_nu_decode, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, y, out, rows, D, width, height, p_sum, part.get());
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -3080,19 +3046,19 @@ int dsg_best_of(int problem, const float* Y, const float* X, int n, long long B,
     if (B == 0 || n == 0) return 0;
     if (eval_args(Y, X, B, D, "dsg_best_of") || !solution || !objective || !round) return fail("dsg_best_of: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    float2* scratch = nullptr;                        // [n] per-round (min, max), then the partials [n][nparts]
+    StreamScratch<float2> scratch;                    // [n] per-round (min, max), then the partials [n][nparts]
     if (problem != DSG_PROBLEM_CO) {
         const int c0 = 0, c1 = problem == DSG_PROBLEM_MSR ? D : 2;
         const int w = c1 - c0, lpr = w >= 64 ? 64 : (w >= 16 ? 16 : (w >= 4 ? 4 : 1));
         const long long want = (B + 4LL * (64 / lpr) - 1) / (4LL * (64 / lpr));
         const int nparts = (int)(want < kEvalParts ? want : kEvalParts);
-        HIPCK(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)n * (1 + nparts) * sizeof(float2), s));
+        HIPCK(scratch.alloc((size_t)n * (1 + nparts), s));
         const unsigned gy = (unsigned)(n < 65535 ? n : 65535);
         hipLaunchKernelGGL(k_best_minmax_partial, dim3(nparts, gy), dim3(256), 0, s, Y, n, B, D, c0, c1, scratch + n);
-        hipLaunchKernelGGL(k_best_minmax_final, dim3(gy), dim3(256), 0, s, scratch + n, n, nparts, scratch);
+        hipLaunchKernelGGL(k_best_minmax_final, dim3(gy), dim3(256), 0, s, scratch + n, n, nparts, scratch.get());
     }
     auto grid = [&](int lpr) { const long long rpb = 4LL * (64 / lpr); return dim3((unsigned)((B + rpb - 1) / rpb)); };
-#define DSG_BEST_MSR(L, Q) hipLaunchKernelGGL((k_best_msr<L, Q>), grid(L), dim3(256), 0, s, Y, X, n, B, D, params[0], scratch, solution, \
+#define DSG_BEST_MSR(L, Q) hipLaunchKernelGGL((k_best_msr<L, Q>), grid(L), dim3(256), 0, s, Y, X, n, B, D, params[0], scratch.get(), solution, \
                                               objective, round, objectives, accumulate, round0)
     if (problem == DSG_PROBLEM_MSR) {
         // lanes per row = k_row_softmax's for this D; Q = k_msr_rate's lanes per row over that (see k_best_msr)
@@ -3106,11 +3072,10 @@ int dsg_best_of(int problem, const float* Y, const float* X, int n, long long B,
         hipLaunchKernelGGL(k_best_co, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, Y, X, n, B, D, solution, objective, round, objectives,
                            accumulate, round0);
     } else {
-        hipLaunchKernelGGL(k_best_nu, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, Y, X, n, B, D, params[0], params[1], params[2], scratch,
+        hipLaunchKernelGGL(k_best_nu, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, Y, X, n, B, D, params[0], params[1], params[2], scratch.get(),
                            solution, objective, round, objectives, accumulate, round0);
     }
 #undef DSG_BEST_MSR
-    if (scratch) HIPCK(hipFreeAsync(scratch, s));
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -3121,8 +3086,8 @@ int dsg_sum_rate_gen(const double* gs, double* schemes, double* rates, long long
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int kMaxIter = 149;                       // the reference leaves its loop when k reaches 150
-    int* flags = nullptr;
-    HIPCK(hipMallocAsync(reinterpret_cast<void**>(&flags), (kMaxIter + 3) * sizeof(int), s));
+    StreamScratch<int> flags;
+    HIPCK(flags.alloc(kMaxIter + 3, s));
     HIPCK(hipMemsetAsync(flags, 0, (kMaxIter + 3) * sizeof(int), s));
     HIPCK(hipMemsetAsync(flags, 1, 1, s));          // flags[0] = 1 (low byte): the dry pass always runs
     const long long n = rows * M;
@@ -3130,7 +3095,7 @@ int dsg_sum_rate_gen(const double* gs, double* schemes, double* rates, long long
     const dim3 grid((unsigned)((rows + 3) / 4));
     const double eps = 0.001;
     double beta = 0.1;
-    hipLaunchKernelGGL(k_sumrate_iter, grid, dim3(256), 0, s, gs, schemes, rows, M, 0.0, eps, flags, flags + 1, 1);
+    hipLaunchKernelGGL(k_sumrate_iter, grid, dim3(256), 0, s, gs, schemes, rows, M, 0.0, eps, flags.get(), flags + 1, 1);
     int k = 1;
     for (int it = 1; it <= kMaxIter; ++it) {
         hipLaunchKernelGGL(k_sumrate_iter, grid, dim3(256), 0, s, gs, schemes, rows, M, beta, eps, flags + it, flags + it + 1, 0);
@@ -3139,7 +3104,6 @@ int dsg_sum_rate_gen(const double* gs, double* schemes, double* rates, long long
         if (k == 150) break;
     }
     hipLaunchKernelGGL(k_sumrate_rates, grid, dim3(256), 0, s, gs, schemes, rates, rows, M);
-    HIPCK(hipFreeAsync(flags, s));
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -3169,8 +3133,9 @@ int dsg_noma_uav_search(const double* qs, const double* fs, int nfs, double* out
     const int tile_pts = rows < 64 ? 256 : kNuMaxTile;
     const int tiles = (kNuGridPts + tile_pts - 1) / tile_pts;
     const long long chunk = std::min<long long>(rows, 16384);   // pass-1 grid: chunk * tiles workgroups (< 2^32 work-items)
-    double* best_rate = nullptr;
-    HIPCK(hipMallocAsync(reinterpret_cast<void**>(&best_rate), (size_t)chunk * tiles * 16, s));
+    StreamScratch<double> scratch;                   // [chunk * tiles] best rates, then as many keys
+    HIPCK(scratch.alloc((size_t)chunk * tiles * 2, s));
+    double* best_rate = scratch;
     unsigned long long* best_key = reinterpret_cast<unsigned long long*>(best_rate + chunk * tiles);
     const NuGenConst cc{sigma_sq, rou_0, H};
     for (long long r0 = 0; r0 < rows; r0 += chunk) {
@@ -3180,7 +3145,6 @@ int dsg_noma_uav_search(const double* qs, const double* fs, int nfs, double* out
         hipLaunchKernelGGL(k_nu_pick, dim3((unsigned)n), dim3(kNuThreads), 0, s, qs + r0 * 6, fs, cc, tiles, best_rate, best_key,
                            out + r0 * 6);
     }
-    HIPCK(hipFreeAsync(best_rate, s));
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -3235,11 +3199,11 @@ int dsg_time_op(dsg_handle* h, int op, int B, int iters, float* ms_avg, void* st
     hipStream_t s = (hipStream_t)stream;
     const int zero = 0;
     HIPCK(hipMemcpyAsync(h->step_dev, &zero, sizeof(int), hipMemcpyHostToDevice, s));
-    RunCtx c{B, 2, cdiv(B, 32), h->ywork, h->eps, h->step_dev, nullptr, false, true};
+    RunCtx c{B, 2, cdiv(B, 32), h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true};
     if (narrow_singles(h, c) && prepare_fused(h, c, s)) return 1;     // exact path: the single-operator table of this context
-    hipEvent_t e0, e1;
-    HIPCK(hipEventCreate(&e0));
-    HIPCK(hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCK(hipEventCreate(e0.put()));
+    HIPCK(hipEventCreate(e1.put()));
     launch_op(h, h->ops[op], c, s);  // warm-up
     HIPCK(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i) launch_op(h, h->ops[op], c, s);
@@ -3247,8 +3211,6 @@ int dsg_time_op(dsg_handle* h, int op, int B, int iters, float* ms_avg, void* st
     HIPCK(hipEventSynchronize(e1));
     float ms = 0.f;
     HIPCK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_avg = ms / iters;
     return 0;
 }
@@ -3270,19 +3232,15 @@ int dsg_box_calibrate(float* out3 /* four floats */, void* stream) {
     HIPCK(hipGetDevice(&devid));
     HIPCK(hipGetDeviceProperties(&prop, devid));
     const int cus = prop.multiProcessorCount;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float* sink = nullptr;
+    Event e0, e1;           // owners: every early return below (a failed 512 MiB allocation beside a large batch) frees what exists
+    DevBuf<float> sink;
     const size_t copy_bytes = (size_t)256 << 20;
-    char* buf = nullptr;
-    struct Guard {          // every early return below (a failed 512 MiB allocation beside a large batch) frees what exists
-        hipEvent_t &a, &b; float*& s; char*& c;
-        ~Guard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (s) (void)hipFree(s); if (c) (void)hipFree(c); }
-    } guard{e0, e1, sink, buf};
-    HIPCK(hipEventCreate(&e0));
-    HIPCK(hipEventCreate(&e1));
-    HIPCK(hipMalloc(&sink, (size_t)cus * 2 * 512 * sizeof(float)));
-    HIPCK(hipMalloc(&buf, 2 * copy_bytes));
-    hipLaunchKernelGGL(dsg::k_calib_fill, dim3(cus * 8), dim3(256), 0, s, reinterpret_cast<uint4*>(buf), 2 * copy_bytes / 16);
+    DevBuf<char> buf;
+    HIPCK(hipEventCreate(e0.put()));
+    HIPCK(hipEventCreate(e1.put()));
+    HIPCK(sink.alloc((size_t)cus * 2 * 512));
+    HIPCK(buf.alloc(2 * copy_bytes));
+    hipLaunchKernelGGL(dsg::k_calib_fill, dim3(cus * 8), dim3(256), 0, s, reinterpret_cast<uint4*>(buf.get()), 2 * copy_bytes / 16);
     auto median5 = [&](auto&& launch, float& ms_out) -> int {
         float t[6];
         for (int rep = 0; rep < 6; ++rep) {      // the first launch is a warm-up
@@ -3299,9 +3257,9 @@ int dsg_box_calibrate(float* out3 /* four floats */, void* stream) {
     // two workgroups of four waves per CU = two waves per SIMD, as the block kernels run
     const int it0 = 3072, it6 = 1536;             // x 48 MFMAs: ~5 ms each at two waves per SIMD
     float ms0 = 0.f, ms6 = 0.f, msc = 0.f;
-    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_mfma<0>, dim3(2 * cus), dim3(256), 0, s, it0, sink); }, ms0)) return 1;
-    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_mfma<6>, dim3(2 * cus), dim3(256), 0, s, it6, sink); }, ms6)) return 1;
-    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_copy, dim3(cus * 8), dim3(256), 0, s, reinterpret_cast<const uint4*>(buf),
+    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_mfma<0>, dim3(2 * cus), dim3(256), 0, s, it0, sink.get()); }, ms0)) return 1;
+    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_mfma<6>, dim3(2 * cus), dim3(256), 0, s, it6, sink.get()); }, ms6)) return 1;
+    if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_copy, dim3(cus * 8), dim3(256), 0, s, reinterpret_cast<const uint4*>(buf.get()),
                                          reinterpret_cast<uint4*>(buf + copy_bytes), copy_bytes / 16); }, msc)) return 1;
     out3[0] = (float)((double)cus * 8 * it0 * 48 * 32768.0 / (ms0 * 1e-3) / 1e12);
     out3[1] = (float)((double)cus * 8 * it6 * 48 / (ms6 * 1e-3) / 1e9);
@@ -3311,7 +3269,7 @@ int dsg_box_calibrate(float* out3 /* four floats */, void* stream) {
     {
         const int panels = 1536;
         float msp = 0.f;
-        if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_panel, dim3(cus), dim3(512), 0, s, reinterpret_cast<const uint4*>(buf),
+        if (median5([&] { hipLaunchKernelGGL(dsg::k_calib_panel, dim3(cus), dim3(512), 0, s, reinterpret_cast<const uint4*>(buf.get()),
                                              reinterpret_cast<const uint4*>(buf + copy_bytes), copy_bytes / 16 - 1, panels, sink); }, msp)) return 1;
         out3[3] = (float)((double)cus * 8 * panels * 48 / (msp * 1e-3) / 1e9);
     }
@@ -3419,12 +3377,12 @@ int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg,
                    lr, beta1, beta2, eps, step0};
     const int bytes = p.lds_floats * 4;
     if (mlp_lds_attr(k_mlp_epoch, bytes)) return 1;
-    // nets whose gradient and moments do not fit in LDS: the gradient in stream-ordered scratch (as the evaluators' reductions); nothing
-    // between the allocation and its release returns early
-    if (!p.onchip) HIPCK(hipMallocAsync(reinterpret_cast<void**>(&e.gws), (size_t)R * p.P * sizeof(float), s));
+    // nets whose gradient and moments do not fit in LDS: the gradient in stream-ordered scratch (as the evaluators' reductions)
+    StreamScratch<float> gws;
+    if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
     hipLaunchKernelGGL(k_mlp_epoch, dim3((unsigned)R), dim3(kMlpThreads), bytes, s, p, e);
     const hipError_t launched = hipGetLastError();
-    const hipError_t freed = e.gws ? hipFreeAsync(e.gws, s) : hipSuccess;
+    const hipError_t freed = gws.release();
     HIPCK(launched);
     HIPCK(freed);
     return 0;

@@ -498,6 +498,62 @@ def test_chunked_graphs_are_keyed_on_the_chunk_size():
     d.record_denoise_path = False
 
 
+def test_regrow_sequences_on_one_handle_match_fresh_handles():
+    """Every buffer of the handle that is dropped and re-allocated while the handle lives, in one sequence on ONE handle, each result
+    bit for bit what a fresh handle gives for the same inputs (injected y_T / noise / draws: no tolerance):
+    (a) sample at 96, 160, 96 rows -- the second call grows the row workspace: graphs and training workspace go with it;
+    (b) sample_chunked over 192 rows as 2 x 96, 6 x 32, 2 x 96 -- the per-chunk seeds and renorm partials regrow;
+    (c) a training step at 64, 128, 64 rows -- the training workspace and its descriptor tables are rebuilt;
+    (d) a graph-mode sample after (c) equals the first call of (a);
+    (e) build a model, sample, drop it (dsg_destroy), five times: destroy then create leaves a working device."""
+    import gc
+    name, T = "msr80", 6
+    plan, p = synth_params(name, 47)
+    cfg = CONFIGS[name]
+    D, C = cfg["input_dim"], cfg["cond_dim"]
+    g = torch.Generator().manual_seed(8)
+    cond = torch.rand(192, C, generator=g).cuda()
+    y_T = torch.randn(192, D, generator=g)
+    z = torch.randn(T - 2, 192, D, generator=g)
+    y = torch.rand(128, D, generator=g).cuda()
+    ts = torch.randint(0, T, (1, 128), generator=g).cuda()
+    noise = torch.randn(128, D, generator=g).cuda()
+    mask = (torch.rand(128, 1, generator=g) < 0.9).float().cuda()
+
+    def fresh():
+        return make_ddpm(name, p, T, "large")
+
+    def sample(d, B, **kw):
+        return d.sample(cond[:B], 1.0, y_T=y_T[:B], noise=z[:, :B].contiguous(), **kw)
+
+    def chunked(d, chunk):
+        return d.sample_chunked(cond, 1.0, chunk, seeds=list(range(192 // chunk)), y_T=y_T, noise=z)
+
+    def step(d, B):
+        for q in d.model.parameters():
+            q.grad = None
+        loss = d(y[:B], cond[:B], ts=ts[:, :B], noise=noise[:B], cond_mask=mask[:B])
+        loss.backward()
+        return float(loss.detach()), d.grad_bucket.detach().clone()
+
+    d = fresh()
+    a = [sample(d, B) for B in (96, 160, 96)]                                   # (a)
+    assert torch.equal(a[0], sample(fresh(), 96)) and torch.equal(a[1], sample(fresh(), 160)) and torch.equal(a[2], a[0])
+    b = [chunked(d, chunk) for chunk in (96, 32, 96)]                           # (b)
+    assert torch.equal(b[0], chunked(fresh(), 96)) and torch.equal(b[1], chunked(fresh(), 32)) and torch.equal(b[2], b[0])
+    c = [step(d, B) for B in (64, 128, 64)]                                     # (c)
+    ref_loss, ref_grad = step(fresh(), 64)
+    assert c[2][0] == ref_loss and torch.equal(c[2][1], ref_grad)
+    assert c[0][0] == ref_loss and torch.equal(c[0][1], ref_grad)
+    assert torch.equal(sample(d, 96, use_graph=True), a[0])                     # (d)
+    for _ in range(5):                                                          # (e)
+        m = fresh()
+        out = sample(m, 96)
+        del m
+        gc.collect()
+        assert torch.equal(out, a[0])
+
+
 def test_sample_many_tile_groups_per_workgroup_vs_oracle():
     """131 072 rows = 8 192 row tiles with both CFG passes: every persistent workgroup (256 CUs x 8 waves) walks
     FOUR tile groups -- the carried-operand seam between a workgroup's tiles (next tile's first operand prepared under the previous
