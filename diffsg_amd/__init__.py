@@ -8,5 +8,7 @@ from .diffusion import generate_cosine_schedule, init_weights  # noqa: F401
 from .ema import ExponentialMovingAverage  # noqa: F401
 from .repeated import BestOf, best_of  # noqa: F401
 from .mtfnn import MTFNN, co_net, msr_net  # noqa: F401
+from .ppo import PPOAgent  # noqa: F401
 
-__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of", "MTFNN", "co_net", "msr_net"]
+__all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of", "MTFNN", "co_net", "msr_net",
+           "PPOAgent"]

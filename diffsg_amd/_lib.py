@@ -56,6 +56,12 @@ class MlpDesc(ctypes.Structure):
     _fields_ = [("n_layers", ctypes.c_int), ("widths", ctypes.c_int * 6), ("n_sig", ctypes.c_int)]
 
 
+class PpoDesc(ctypes.Structure):
+    _fields_ = [("state_dim", ctypes.c_int), ("action_dim", ctypes.c_int), ("hidden", ctypes.c_int * 3), ("env", ctypes.c_int),
+                ("scaler_min", ctypes.c_double), ("scaler_max", ctypes.c_double), ("W", ctypes.c_double),
+                ("width", ctypes.c_double), ("height", ctypes.c_double), ("P_sum", ctypes.c_double)]
+
+
 class UNetDesc(ctypes.Structure):
     _fields_ = [("input_dim", ctypes.c_int), ("proj_dim", ctypes.c_int), ("cond_dim", ctypes.c_int),
                 ("n_res", ctypes.c_int), ("dims", ctypes.c_int * MAX_RES), ("n_blocks", ctypes.c_int)]
@@ -208,6 +214,12 @@ _SIGS = {
     "dsg_mlp_loss_grad": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dsg_mlp_train_epoch": (ctypes.c_int, [ctypes.POINTER(MlpDesc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p]),
+    "dsg_ppo_param_total": (ctypes.c_int, [ctypes.POINTER(PpoDesc)]),
+    "dsg_ppo_forward": (ctypes.c_int, [ctypes.POINTER(PpoDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_longlong, ctypes.c_void_p]),
+    "dsg_ppo_loss_grad": (ctypes.c_int, [ctypes.POINTER(PpoDesc)] + [ctypes.c_void_p] * 5 + [ctypes.c_longlong] + [ctypes.c_void_p] * 5),
+    "dsg_ppo_train_epoch": (ctypes.c_int, [ctypes.POINTER(PpoDesc)] + [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_void_p]),
     "dsg_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong,

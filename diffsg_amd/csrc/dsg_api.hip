@@ -16,6 +16,7 @@
 #include "dsg_cogen.hpp"
 #include "dsg_nugen.hpp"
 #include "dsg_mlp.hpp"
+#include "dsg_ppo.hpp"
 #include "dsg_own.hpp"
 #include "../../include/diffsg.h"
 
@@ -3385,6 +3386,147 @@ int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg,
     const hipError_t freed = gws.release();
     HIPCK(launched);
     HIPCK(freed);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- PPO baseline (dsg_ppo.hpp)
+namespace {
+// Validates the descriptor and lays the workgroup's LDS out: scalar slots | parameters | tile area (the state tile, every layer's
+// activations of both nets, the targets) [| gradient | exp_avg | exp_avg_sq when `epoch` and they fit].  The tile height and the
+// on-chip choice depend on the descriptor alone, so that dsg_ppo_loss_grad and dsg_ppo_train_epoch sum a batch's rows in the same order.
+int ppo_plan(const dsg_ppo_desc* d, PpoPlan* p, bool epoch, const char* who, bool need_env = true) {
+    if (!d) return fail("%s: null descriptor", who);
+    if (d->state_dim < 1 || d->state_dim > kMlpMaxIO) return fail("%s: state_dim = %d (1 .. %d)", who, d->state_dim, kMlpMaxIO);
+    if (d->action_dim < 1 || d->action_dim > kMlpMaxIO) return fail("%s: action_dim = %d (1 .. %d)", who, d->action_dim, kMlpMaxIO);
+    for (int l = 0; l < 3; ++l)
+        if (d->hidden[l] < 1 || d->hidden[l] > kMlpMaxHidden) return fail("%s: hidden[%d] = %d (1 .. %d)", who, l, d->hidden[l], kMlpMaxHidden);
+    const int S = d->state_dim, A = d->action_dim;
+    switch (d->env) {
+        case kPpoCO: if (S != 3 * A) return fail("%s: CO wants state_dim = 3 * action_dim, got %d and %d", who, S, A); break;
+        case kPpoMSR: if (S != A) return fail("%s: MSR wants state_dim = action_dim, got %d and %d", who, S, A); break;
+        case kPpoNU:
+            if (A < 3 || A - 2 > kNuMaxUsers || S != 2 * (A - 2))
+                return fail("%s: NU wants action_dim = K + 2, state_dim = 2 K with 1 <= K <= %d, got %d and %d", who, kNuMaxUsers, A, S);
+            break;
+        case DSG_PPO_NONE: if (need_env) return fail("%s: env = DSG_PPO_NONE; the call needs an environment (0 CO, 1 MSR, 2 NU)", who); break;
+        default: return fail("%s: env = %d (0 CO, 1 MSR, 2 NU)", who, d->env);
+    }
+    memset(p, 0, sizeof *p);
+    p->S = S; p->A = A; p->env = d->env;
+    p->lo = (float)d->scaler_min; p->span = (float)(d->scaler_max - d->scaler_min); p->W = (float)d->W;
+    p->width = (float)d->width; p->height = (float)d->height; p->p_sum = (float)d->P_sum;
+    int off = A, row = S | 1;                           // log_std[A] leads the flat vector; the state tile is shared by the two nets
+    for (int n = 0; n < 2; ++n) {
+        p->w[n][0] = S; p->w[n][1] = d->hidden[0]; p->w[n][2] = d->hidden[1]; p->w[n][3] = d->hidden[2]; p->w[n][4] = n == 0 ? 1 : A;
+        for (int l = 0; l < 4; ++l) {
+            p->woff[n][l] = off; off += p->w[n][l + 1] * p->w[n][l];
+            p->boff[n][l] = off; off += p->w[n][l + 1];
+            row += p->w[n][l + 1] | 1;
+        }
+    }
+    p->P = off;
+    row += A | 1;                                       // the targets
+    int TR = 64;
+    while (TR > 16 && kPpoScal + p->P + TR * row > kMlpLdsFloats) TR >>= 1;
+    if (kPpoScal + p->P + TR * row > kMlpLdsFloats) return fail("%s: the two nets (%d parameters) do not fit in LDS", who, p->P);
+    p->TR = TR;
+    p->tr_shift = TR == 64 ? 6 : (TR == 32 ? 5 : 4);
+    int a = TR * (S | 1);
+    for (int n = 0; n < 2; ++n) {
+        p->aoff[n][0] = 0; p->astr[n][0] = S | 1;
+        for (int l = 1; l <= 4; ++l) { p->aoff[n][l] = a; p->astr[n][l] = p->w[n][l] | 1; a += TR * p->astr[n][l]; }
+    }
+    p->yoff = a; p->ystr = A | 1; a += TR * p->ystr;
+    p->act_floats = a;
+    p->lds_floats = kPpoScal + p->P + a;
+    p->onchip = epoch && p->lds_floats + 3 * p->P <= kMlpLdsFloats;
+    if (p->onchip) p->lds_floats += 3 * p->P;
+    return 0;
+}
+// The batch buffer ([rows][2A + 2]) goes behind everything else in LDS where it fits (its offset), else into a workspace (-1).
+int ppo_buf_off(const PpoPlan& p, long long rows) {
+    return p.lds_floats + rows * (2 * p.A + 2) <= kMlpLdsFloats ? p.lds_floats : -1;
+}
+}  // namespace
+
+extern "C" {
+
+int dsg_ppo_param_total(const dsg_ppo_desc* desc) {
+    PpoPlan p;
+    if (ppo_plan(desc, &p, false, "dsg_ppo_param_total", false)) return -1;
+    return p.P;
+}
+
+int dsg_ppo_forward(const dsg_ppo_desc* desc, const float* params, const float* x, float* mu_out, float* value_out, long long rows,
+                    void* stream) {
+    PpoPlan p;
+    if (ppo_plan(desc, &p, false, "dsg_ppo_forward", false)) return 1;
+    if (rows < 0) return fail("dsg_ppo_forward: rows = %lld", rows);
+    if (rows == 0) return 0;
+    if (!params || !x || !mu_out || !value_out) return fail("dsg_ppo_forward: null argument");
+    const int bytes = p.lds_floats * 4;
+    if (mlp_lds_attr(k_ppo_forward, bytes)) return 1;
+    const long long ntiles = (rows + p.TR - 1) / p.TR;
+    hipLaunchKernelGGL(k_ppo_forward, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x,
+                       mu_out, value_out, rows);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int dsg_ppo_loss_grad(const dsg_ppo_desc* desc, const float* params, const float* x, const float* y, const float* old_logp,
+                      const float* noise, long long rows, float* out3, float* new_logp_out, float* reward_out, float* grad_flat,
+                      void* stream) {
+    PpoPlan p;
+    if (ppo_plan(desc, &p, false, "dsg_ppo_loss_grad")) return 1;
+    if (rows < 0 || rows > 2147483647LL / (2 * kMlpMaxIO + 2))
+        return fail("dsg_ppo_loss_grad: rows = %lld (0 .. %lld)", rows, 2147483647LL / (2 * kMlpMaxIO + 2));
+    if (rows == 0) return 0;
+    if (!params || !x || !y || !old_logp || !noise || !out3 || !new_logp_out || !reward_out || !grad_flat)
+        return fail("dsg_ppo_loss_grad: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int buf_off = ppo_buf_off(p, rows);
+    const int bytes = (buf_off >= 0 ? buf_off + (int)rows * (2 * p.A + 2) : p.lds_floats) * 4;
+    if (mlp_lds_attr(k_ppo_loss_grad, bytes)) return 1;
+    StreamScratch<float> ws;
+    if (buf_off < 0) HIPCK(ws.alloc((size_t)rows * (2 * p.A + 2), s));
+    const PpoBatchIO io{x, y, old_logp, noise, nullptr, new_logp_out, reward_out, rows};
+    hipLaunchKernelGGL(k_ppo_loss_grad, dim3(1), dim3(kMlpThreads), bytes, s, p, params, io, (int)rows, buf_off, ws.get(), out3, grad_flat);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t freed = ws.release();
+    HIPCK(launched);
+    HIPCK(freed);
+    return 0;
+}
+
+int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
+                        float* old_logp, const float* noise, const int* perm, int N, int batch, double lr, double beta1, double beta2,
+                        double eps, long long step0, float* batch_out, int R, void* stream) {
+    PpoPlan p;
+    if (ppo_plan(desc, &p, true, "dsg_ppo_train_epoch")) return 1;
+    if (N < 0 || batch < 1 || R < 1 || step0 < 0) return fail("dsg_ppo_train_epoch: N = %d, batch = %d, R = %d, step0 = %lld", N, batch, R, step0);
+    if (N > 2147483647 / (2 * kMlpMaxIO + 2)) return fail("dsg_ppo_train_epoch: N = %d rows (at most %d)", N, 2147483647 / (2 * kMlpMaxIO + 2));
+    if (N == 0) return 0;
+    if (!params || !exp_avg || !exp_avg_sq || !X || !Y || !old_logp || !noise || !perm || !batch_out)
+        return fail("dsg_ppo_train_epoch: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int bufrows = batch < N ? batch : N;
+    const int buf_off = ppo_buf_off(p, bufrows);
+    PpoEpochArgs e{params, exp_avg, exp_avg_sq, nullptr, nullptr, X, Y, old_logp, noise, perm, batch_out, N, batch,
+                   (int)(((long long)N + batch - 1) / batch), bufrows, buf_off, lr, beta1, beta2, eps, step0};
+    const int bytes = (buf_off >= 0 ? buf_off + bufrows * (2 * p.A + 2) : p.lds_floats) * 4;
+    if (mlp_lds_attr(k_ppo_epoch, bytes)) return 1;
+    // what does not fit in LDS lives in stream-ordered scratch: the gradient (with the moments in place) and / or the batch buffer
+    StreamScratch<float> gws, bws;
+    if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
+    if (buf_off < 0) { HIPCK(bws.alloc((size_t)R * bufrows * (2 * p.A + 2), s)); e.bufws = bws; }
+    hipLaunchKernelGGL(k_ppo_epoch, dim3((unsigned)R), dim3(kMlpThreads), bytes, s, p, e);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t freed = gws.release(), freed2 = bws.release();
+    HIPCK(launched);
+    HIPCK(freed);
+    HIPCK(freed2);
     return 0;
 }
 

@@ -310,6 +310,48 @@ int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg,
                         const int* perm, int N, int batch, double lr, double beta1, double beta2, double eps, long long step0,
                         float* batch_loss, int R, void* stream);
 
+/* ---- The PPO baseline (baselines/PPO.py: class PPOAgent and the loops of ppo_co / ppo_msr / ppo_nu), csrc/dsg_ppo.hpp.
+ * A critic state_dim -> hidden[0] -> hidden[1] -> hidden[2] -> 1 and an actor ... -> action_dim, tanh after every layer but the last,
+ * and a state-independent log_std[action_dim]; the reward is one environment step of CO, MSR or NU (env) with the scalars below.
+ * state_dim, action_dim <= 128, hidden widths <= 64 (the reference: 64, 16, 32); CO wants state_dim = 3 action_dim, MSR state_dim =
+ * action_dim, NU action_dim = K + 2 and state_dim = 2 K (K <= 32); nets too large for one compute unit's LDS and anything else are
+ * refused with a message, nothing is launched.  Parameters (gradients, Adam moments) travel as ONE flat float32 vector in the reference's
+ * state-dict order: log_std[A], critic.{0,2,4,6}.{weight,bias}, actor.{0,2,4,6}.{weight,bias}.  No handle.  Stream-ordered; rows == 0
+ * (N == 0) launches nothing. */
+enum { DSG_PPO_NONE = -1, DSG_PPO_CO = 0, DSG_PPO_MSR = 1, DSG_PPO_NU = 2 };   /* NONE: dsg_ppo_param_total / dsg_ppo_forward only */
+typedef struct {
+    int state_dim, action_dim;
+    int hidden[3];
+    int env;
+    double scaler_min, scaler_max;  /* CO, MSR: the state is x * (scaler_max - scaler_min) + scaler_min */
+    double W;                       /* MSR: the power budget the softmaxed action is scaled by */
+    double width, height, P_sum;    /* NU: area and power budget of the decoder */
+} dsg_ppo_desc;
+/* Length of the flat parameter vector, or -1 (message in the last error) if the descriptor is refused. */
+int dsg_ppo_param_total(const dsg_ppo_desc* desc);
+/* mu_out[rows][action_dim] = actor(x), value_out[rows] = critic(x), row-parallel.  Nothing is sampled. */
+int dsg_ppo_forward(const dsg_ppo_desc* desc, const float* params, const float* x, float* mu_out, float* value_out, long long rows,
+                    void* stream);
+/* ONE batch of PPO.py:140-154, no update: a = noise * exp(log_std) + mu, new_logp = Normal(mu, std).log_prob(a), ratio = exp(new_logp -
+ * old_logp), reward = 1 / (|objective(x, softmax(a)) - objective(x, y)| + offset) (NU: the action decoded with the batch-wide min / max,
+ * every user at the origin as in the reference's nu_env_step), returns = reward + 0.99 * 3.8, advantage = returns - value (NOT detached).
+ * out3 = {actor loss (clipped surrogate, epsilon 0.2), critic loss (MSE), sum of rewards}; new_logp_out[rows][A]; reward_out[rows];
+ * grad_flat[P] = d (actor loss + critic loss) / d parameter, the log_std slots written as zeros.  x [rows][S], y, old_logp, noise
+ * [rows][A].  One workgroup, every sum over rows in one fixed order: deterministic, and the per-batch arithmetic of the epoch call. */
+int dsg_ppo_loss_grad(const dsg_ppo_desc* desc, const float* params, const float* x, const float* y, const float* old_logp,
+                      const float* noise, long long rows, float* out3, float* new_logp_out, float* reward_out, float* grad_flat,
+                      void* stream);
+/* One whole epoch in one launch: for k = 0 .. ceil(N / batch) - 1 the rows perm[k * batch .. min((k + 1) * batch, N)) (int32 on the
+ * device, clamped into [0, N)), the batch above, and one Adam step (torch.optim.Adam, no weight decay) numbered step0 + k + 1 over the
+ * critic and actor range (log_std is never updated); batch_out[k] receives the batch's out3.  R >= 1 independent agents train in the same
+ * launch on the same X / Y, one workgroup each: params, exp_avg, exp_avg_sq [R][P]; old_logp [R][N][A] indexed by DATASET row, read and
+ * then overwritten with this epoch's new_logp; noise [R][N][A] indexed by position in the epoch; perm [R][N]; batch_out [R][nb][3].
+ * No atomics: run-to-run identical, replica r identical to an R = 1 call on its slices, and every batch bit-identical to
+ * dsg_ppo_loss_grad on the gathered rows followed by dsg_adam_step over the critic and actor range. */
+int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
+                        float* old_logp, const float* noise, const int* perm, int N, int batch, double lr, double beta1, double beta2,
+                        double eps, long long step0, float* batch_out, int R, void* stream);
+
 /* Measurement hooks for bench.py: the per-step operator list and a timed replay of one operator's kernel with HIP
  * events on `stream` (rows = B rows, both passes, as inside dsg_sample). */
 int dsg_op_count(const dsg_handle* h);
