@@ -3279,11 +3279,39 @@ int dsg_box_calibrate(float* out3 /* four floats */, void* stream) {
 
 }  // extern "C"
 
-// ---- MTFNN baseline (dsg_mlp.hpp)
+// ---- the small-net baselines: MTFNN (dsg_mlp.hpp) and PPO (dsg_ppo.hpp)
 namespace {
+// One net's part of a plan, from its widths w[0 .. L]: the weight / bias offsets in the flat vector from *off on, and from activation
+// a0 on the odd row strides and the offsets within ONE tile row from *row on (plan_tile scales them by the tile height).
+void net_layout(int L, const int* w, int* woff, int* boff, int a0, int* aoff, int* astr, int* off, int* row) {
+    for (int l = 0; l < L; ++l) {
+        woff[l] = *off; *off += w[l + 1] * w[l];
+        boff[l] = *off; *off += w[l + 1];
+    }
+    for (int l = a0; l <= L; ++l) { astr[l] = w[l] | 1; aoff[l] = *row; *row += astr[l]; }
+}
+// Completes a plan whose P, strides and per-row offsets are in, for `scal` scalar slots and tile rows of `row` floats.  The tile height
+// is 64 rows, or 32 or 16 where the slots, the parameters and the tile exceed the LDS (false: 16 rows do too); gradient and both Adam
+// moments go behind the tile when the call is an epoch and they fit.  Both depend on the descriptor alone, so that the loss_grad and
+// the train_epoch call of a baseline sum a batch's rows in the same order.
+template <typename Plan>
+bool plan_tile(Plan* p, int scal, int row, bool epoch) {
+    int TR = 64;
+    while (TR > 16 && scal + p->P + TR * row > kMlpLdsFloats) TR >>= 1;
+    if (scal + p->P + TR * row > kMlpLdsFloats) return false;
+    p->TR = TR;
+    p->tr_shift = TR == 64 ? 6 : (TR == 32 ? 5 : 4);
+    int* aoff = reinterpret_cast<int*>(p->aoff);        // one net's offsets, or both nets' (the unused entries are zero)
+    for (size_t i = 0; i < sizeof p->aoff / sizeof(int); ++i) aoff[i] *= TR;
+    p->yoff *= TR;
+    p->act_floats = TR * row;
+    p->lds_floats = scal + p->P + p->act_floats;
+    p->onchip = epoch && p->lds_floats + 3 * p->P <= kMlpLdsFloats;
+    if (p->onchip) p->lds_floats += 3 * p->P;
+    return true;
+}
 // Validates the descriptor and lays the workgroup's LDS out: scalar slots | parameters | tile area (activations of every layer, targets)
-// [| gradient | exp_avg | exp_avg_sq when `epoch` and they fit].  The tile height depends on the net's shape alone, so that
-// dsg_mlp_loss_grad and dsg_mlp_train_epoch sum a batch's rows in the same order.
+// [| gradient | exp_avg | exp_avg_sq].
 int mlp_plan(const dsg_mlp_desc* d, MlpPlan* p, bool epoch, const char* who) {
     if (!d) return fail("%s: null descriptor", who);
     const int L = d->n_layers;
@@ -3297,105 +3325,15 @@ int mlp_plan(const dsg_mlp_desc* d, MlpPlan* p, bool epoch, const char* who) {
     memset(p, 0, sizeof *p);
     p->L = L;
     p->n_sig = d->n_sig;
-    int off = 0, row = 0;
     for (int l = 0; l <= L; ++l) p->w[l] = d->widths[l];
-    for (int l = 0; l < L; ++l) {
-        p->woff[l] = off; off += p->w[l + 1] * p->w[l];
-        p->boff[l] = off; off += p->w[l + 1];
-    }
-    p->P = off;
-    for (int l = 0; l <= L; ++l) row += p->w[l] | 1;
-    row += p->w[L] | 1;                                   // the targets
-    int TR = 64;
-    while (TR > 16 && kMlpScal + p->P + TR * row > kMlpLdsFloats) TR >>= 1;
-    if (kMlpScal + p->P + TR * row > kMlpLdsFloats) return fail("%s: the net does not fit in LDS", who);   // not reachable within the width limits
-    p->TR = TR;
-    p->tr_shift = TR == 64 ? 6 : (TR == 32 ? 5 : 4);
-    int a = 0;
-    for (int l = 0; l <= L; ++l) { p->aoff[l] = a; p->astr[l] = p->w[l] | 1; a += TR * p->astr[l]; }
-    p->yoff = a; p->ystr = p->w[L] | 1; a += TR * p->ystr;
-    p->act_floats = a;
-    p->lds_floats = kMlpScal + p->P + a;
-    p->onchip = epoch && p->lds_floats + 3 * p->P <= kMlpLdsFloats;
-    if (p->onchip) p->lds_floats += 3 * p->P;
+    int row = 0;
+    net_layout(L, p->w, p->woff, p->boff, 0, p->aoff, p->astr, &p->P, &row);
+    p->yoff = row; p->ystr = p->w[L] | 1; row += p->ystr;      // the targets
+    if (!plan_tile(p, kMlpScal, row, epoch)) return fail("%s: the net does not fit in LDS", who);     // not reachable within the width limits
     return 0;
 }
-template <typename K>
-int mlp_lds_attr(K kernel, int bytes) {
-    if (bytes > 65536) HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int dsg_mlp_param_total(const dsg_mlp_desc* desc) {
-    MlpPlan p;
-    if (mlp_plan(desc, &p, false, "dsg_mlp_param_total")) return -1;
-    return p.P;
-}
-
-int dsg_mlp_forward(const dsg_mlp_desc* desc, const float* params, const float* x, float* out, long long rows, void* stream) {
-    MlpPlan p;
-    if (mlp_plan(desc, &p, false, "dsg_mlp_forward")) return 1;
-    if (rows < 0) return fail("dsg_mlp_forward: rows = %lld", rows);
-    if (rows == 0) return 0;
-    if (!params || !x || !out) return fail("dsg_mlp_forward: null argument");
-    const int bytes = p.lds_floats * 4;
-    if (mlp_lds_attr(k_mlp_forward, bytes)) return 1;
-    const long long ntiles = (rows + p.TR - 1) / p.TR;
-    hipLaunchKernelGGL(k_mlp_forward, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x,
-                       out, rows);
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-int dsg_mlp_loss_grad(const dsg_mlp_desc* desc, const float* params, const float* x, const float* y, long long rows, float* loss_out,
-                      float* grad_flat, void* stream) {
-    MlpPlan p;
-    if (mlp_plan(desc, &p, false, "dsg_mlp_loss_grad")) return 1;
-    if (rows < 0 || rows > 2147483647LL / kMlpMaxIO) return fail("dsg_mlp_loss_grad: rows = %lld (0 .. %lld)", rows, 2147483647LL / kMlpMaxIO);
-    if (rows == 0) return 0;
-    if (!params || !x || !y || !loss_out || !grad_flat) return fail("dsg_mlp_loss_grad: null argument");
-    const int bytes = p.lds_floats * 4;
-    if (mlp_lds_attr(k_mlp_loss_grad, bytes)) return 1;
-    hipLaunchKernelGGL(k_mlp_loss_grad, dim3(1), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x, y, (int)rows, loss_out, grad_flat);
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
-                        const int* perm, int N, int batch, double lr, double beta1, double beta2, double eps, long long step0, float* batch_loss,
-                        int R, void* stream) {
-    MlpPlan p;
-    if (mlp_plan(desc, &p, true, "dsg_mlp_train_epoch")) return 1;
-    if (N < 0 || batch < 1 || R < 1 || step0 < 0) return fail("dsg_mlp_train_epoch: N = %d, batch = %d, R = %d, step0 = %lld", N, batch, R, step0);
-    if (N > 2147483647 / kMlpMaxIO) return fail("dsg_mlp_train_epoch: N = %d rows (at most %d)", N, 2147483647 / kMlpMaxIO);
-    if (N == 0) return 0;
-    if (!params || !exp_avg || !exp_avg_sq || !X || !Y || !perm || !batch_loss) return fail("dsg_mlp_train_epoch: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    MlpEpochArgs e{params, exp_avg, exp_avg_sq, nullptr, X, Y, perm, batch_loss, N, batch, (int)(((long long)N + batch - 1) / batch),
-                   lr, beta1, beta2, eps, step0};
-    const int bytes = p.lds_floats * 4;
-    if (mlp_lds_attr(k_mlp_epoch, bytes)) return 1;
-    // nets whose gradient and moments do not fit in LDS: the gradient in stream-ordered scratch (as the evaluators' reductions)
-    StreamScratch<float> gws;
-    if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
-    hipLaunchKernelGGL(k_mlp_epoch, dim3((unsigned)R), dim3(kMlpThreads), bytes, s, p, e);
-    const hipError_t launched = hipGetLastError();
-    const hipError_t freed = gws.release();
-    HIPCK(launched);
-    HIPCK(freed);
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- PPO baseline (dsg_ppo.hpp)
-namespace {
 // Validates the descriptor and lays the workgroup's LDS out: scalar slots | parameters | tile area (the state tile, every layer's
-// activations of both nets, the targets) [| gradient | exp_avg | exp_avg_sq when `epoch` and they fit].  The tile height and the
-// on-chip choice depend on the descriptor alone, so that dsg_ppo_loss_grad and dsg_ppo_train_epoch sum a batch's rows in the same order.
+// activations of both nets, the targets) [| gradient | exp_avg | exp_avg_sq].
 int ppo_plan(const dsg_ppo_desc* d, PpoPlan* p, bool epoch, const char* who, bool need_env = true) {
     if (!d) return fail("%s: null descriptor", who);
     if (d->state_dim < 1 || d->state_dim > kMlpMaxIO) return fail("%s: state_dim = %d (1 .. %d)", who, d->state_dim, kMlpMaxIO);
@@ -3417,41 +3355,87 @@ int ppo_plan(const dsg_ppo_desc* d, PpoPlan* p, bool epoch, const char* who, boo
     p->S = S; p->A = A; p->env = d->env;
     p->lo = (float)d->scaler_min; p->span = (float)(d->scaler_max - d->scaler_min); p->W = (float)d->W;
     p->width = (float)d->width; p->height = (float)d->height; p->p_sum = (float)d->P_sum;
-    int off = A, row = S | 1;                           // log_std[A] leads the flat vector; the state tile is shared by the two nets
+    p->P = A;                                           // log_std[A] leads the flat vector
+    int row = S | 1;                                    // the state tile, at offset 0, is activation 0 of both nets
     for (int n = 0; n < 2; ++n) {
         p->w[n][0] = S; p->w[n][1] = d->hidden[0]; p->w[n][2] = d->hidden[1]; p->w[n][3] = d->hidden[2]; p->w[n][4] = n == 0 ? 1 : A;
-        for (int l = 0; l < 4; ++l) {
-            p->woff[n][l] = off; off += p->w[n][l + 1] * p->w[n][l];
-            p->boff[n][l] = off; off += p->w[n][l + 1];
-            row += p->w[n][l + 1] | 1;
-        }
+        p->astr[n][0] = S | 1;
+        net_layout(4, p->w[n], p->woff[n], p->boff[n], 1, p->aoff[n], p->astr[n], &p->P, &row);
     }
-    p->P = off;
-    row += A | 1;                                       // the targets
-    int TR = 64;
-    while (TR > 16 && kPpoScal + p->P + TR * row > kMlpLdsFloats) TR >>= 1;
-    if (kPpoScal + p->P + TR * row > kMlpLdsFloats) return fail("%s: the two nets (%d parameters) do not fit in LDS", who, p->P);
-    p->TR = TR;
-    p->tr_shift = TR == 64 ? 6 : (TR == 32 ? 5 : 4);
-    int a = TR * (S | 1);
-    for (int n = 0; n < 2; ++n) {
-        p->aoff[n][0] = 0; p->astr[n][0] = S | 1;
-        for (int l = 1; l <= 4; ++l) { p->aoff[n][l] = a; p->astr[n][l] = p->w[n][l] | 1; a += TR * p->astr[n][l]; }
-    }
-    p->yoff = a; p->ystr = A | 1; a += TR * p->ystr;
-    p->act_floats = a;
-    p->lds_floats = kPpoScal + p->P + a;
-    p->onchip = epoch && p->lds_floats + 3 * p->P <= kMlpLdsFloats;
-    if (p->onchip) p->lds_floats += 3 * p->P;
+    p->yoff = row; p->ystr = A | 1; row += p->ystr;     // the targets
+    if (!plan_tile(p, kPpoScal, row, epoch)) return fail("%s: the two nets (%d parameters) do not fit in LDS", who, p->P);
     return 0;
 }
 // The batch buffer ([rows][2A + 2]) goes behind everything else in LDS where it fits (its offset), else into a workspace (-1).
 int ppo_buf_off(const PpoPlan& p, long long rows) {
     return p.lds_floats + rows * (2 * p.A + 2) <= kMlpLdsFloats ? p.lds_floats : -1;
 }
+// What the two epoch entry points check alike; cols: the widest row the kernel indexes with an int.
+int epoch_args(const char* who, int N, int batch, int R, long long step0, int cols) {
+    if (N < 0 || batch < 1 || R < 1 || step0 < 0) return fail("%s: N = %d, batch = %d, R = %d, step0 = %lld", who, N, batch, R, step0);
+    if (N > 2147483647 / cols) return fail("%s: N = %d rows (at most %d)", who, N, 2147483647 / cols);
+    return 0;
+}
+// One launch of a baseline kernel: `grid` workgroups of kMlpThreads with `bytes` of dynamic LDS (above 64 KiB the kernel's limit is
+// raised first).  The stream-ordered scratch the launch reads is released behind it; the launch error is reported before a release error.
+template <typename K, typename... Args>
+int baseline_launch(K kernel, long long grid, int bytes, hipStream_t s, std::initializer_list<StreamScratch<float>*> scratch, Args... args) {
+    if (bytes > 65536) HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kMlpThreads), bytes, s, args...);
+    hipError_t err = hipGetLastError();
+    for (StreamScratch<float>* ws : scratch) {
+        const hipError_t freed = ws->release();
+        if (err == hipSuccess) err = freed;
+    }
+    HIPCK(err);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
+
+int dsg_mlp_param_total(const dsg_mlp_desc* desc) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_param_total")) return -1;
+    return p.P;
+}
+
+int dsg_mlp_forward(const dsg_mlp_desc* desc, const float* params, const float* x, float* out, long long rows, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_forward")) return 1;
+    if (rows < 0) return fail("dsg_mlp_forward: rows = %lld", rows);
+    if (rows == 0) return 0;
+    if (!params || !x || !out) return fail("dsg_mlp_forward: null argument");
+    const long long ntiles = (rows + p.TR - 1) / p.TR;
+    return baseline_launch(k_mlp_forward, ntiles < 2048 ? ntiles : 2048, p.lds_floats * 4, (hipStream_t)stream, {}, p, params, x, out, rows);
+}
+
+int dsg_mlp_loss_grad(const dsg_mlp_desc* desc, const float* params, const float* x, const float* y, long long rows, float* loss_out,
+                      float* grad_flat, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, false, "dsg_mlp_loss_grad")) return 1;
+    if (rows < 0 || rows > 2147483647LL / kMlpMaxIO) return fail("dsg_mlp_loss_grad: rows = %lld (0 .. %lld)", rows, 2147483647LL / kMlpMaxIO);
+    if (rows == 0) return 0;
+    if (!params || !x || !y || !loss_out || !grad_flat) return fail("dsg_mlp_loss_grad: null argument");
+    return baseline_launch(k_mlp_loss_grad, 1, p.lds_floats * 4, (hipStream_t)stream, {}, p, params, x, y, (int)rows, loss_out, grad_flat);
+}
+
+int dsg_mlp_train_epoch(const dsg_mlp_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
+                        const int* perm, int N, int batch, double lr, double beta1, double beta2, double eps, long long step0, float* batch_loss,
+                        int R, void* stream) {
+    MlpPlan p;
+    if (mlp_plan(desc, &p, true, "dsg_mlp_train_epoch")) return 1;
+    if (epoch_args("dsg_mlp_train_epoch", N, batch, R, step0, kMlpMaxIO)) return 1;
+    if (N == 0) return 0;
+    if (!params || !exp_avg || !exp_avg_sq || !X || !Y || !perm || !batch_loss) return fail("dsg_mlp_train_epoch: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    MlpEpochArgs e{params, exp_avg, exp_avg_sq, nullptr, X, Y, perm, batch_loss, N, batch, (int)(((long long)N + batch - 1) / batch),
+                   {lr, beta1, beta2, eps, step0}};
+    // nets whose gradient and moments do not fit in LDS: the gradient in stream-ordered scratch (as the evaluators' reductions)
+    StreamScratch<float> gws;
+    if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
+    return baseline_launch(k_mlp_epoch, R, p.lds_floats * 4, s, {&gws}, p, e);
+}
 
 int dsg_ppo_param_total(const dsg_ppo_desc* desc) {
     PpoPlan p;
@@ -3466,13 +3450,9 @@ int dsg_ppo_forward(const dsg_ppo_desc* desc, const float* params, const float* 
     if (rows < 0) return fail("dsg_ppo_forward: rows = %lld", rows);
     if (rows == 0) return 0;
     if (!params || !x || !mu_out || !value_out) return fail("dsg_ppo_forward: null argument");
-    const int bytes = p.lds_floats * 4;
-    if (mlp_lds_attr(k_ppo_forward, bytes)) return 1;
     const long long ntiles = (rows + p.TR - 1) / p.TR;
-    hipLaunchKernelGGL(k_ppo_forward, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(kMlpThreads), bytes, (hipStream_t)stream, p, params, x,
-                       mu_out, value_out, rows);
-    HIPCK(hipGetLastError());
-    return 0;
+    return baseline_launch(k_ppo_forward, ntiles < 2048 ? ntiles : 2048, p.lds_floats * 4, (hipStream_t)stream, {}, p, params, x, mu_out,
+                           value_out, rows);
 }
 
 int dsg_ppo_loss_grad(const dsg_ppo_desc* desc, const float* params, const float* x, const float* y, const float* old_logp,
@@ -3488,16 +3468,10 @@ int dsg_ppo_loss_grad(const dsg_ppo_desc* desc, const float* params, const float
     hipStream_t s = (hipStream_t)stream;
     const int buf_off = ppo_buf_off(p, rows);
     const int bytes = (buf_off >= 0 ? buf_off + (int)rows * (2 * p.A + 2) : p.lds_floats) * 4;
-    if (mlp_lds_attr(k_ppo_loss_grad, bytes)) return 1;
     StreamScratch<float> ws;
     if (buf_off < 0) HIPCK(ws.alloc((size_t)rows * (2 * p.A + 2), s));
     const PpoBatchIO io{x, y, old_logp, noise, nullptr, new_logp_out, reward_out, rows};
-    hipLaunchKernelGGL(k_ppo_loss_grad, dim3(1), dim3(kMlpThreads), bytes, s, p, params, io, (int)rows, buf_off, ws.get(), out3, grad_flat);
-    const hipError_t launched = hipGetLastError();
-    const hipError_t freed = ws.release();
-    HIPCK(launched);
-    HIPCK(freed);
-    return 0;
+    return baseline_launch(k_ppo_loss_grad, 1, bytes, s, {&ws}, p, params, io, (int)rows, buf_off, ws.get(), out3, grad_flat);
 }
 
 int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg, float* exp_avg_sq, const float* X, const float* Y,
@@ -3505,8 +3479,7 @@ int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg,
                         double eps, long long step0, float* batch_out, int R, void* stream) {
     PpoPlan p;
     if (ppo_plan(desc, &p, true, "dsg_ppo_train_epoch")) return 1;
-    if (N < 0 || batch < 1 || R < 1 || step0 < 0) return fail("dsg_ppo_train_epoch: N = %d, batch = %d, R = %d, step0 = %lld", N, batch, R, step0);
-    if (N > 2147483647 / (2 * kMlpMaxIO + 2)) return fail("dsg_ppo_train_epoch: N = %d rows (at most %d)", N, 2147483647 / (2 * kMlpMaxIO + 2));
+    if (epoch_args("dsg_ppo_train_epoch", N, batch, R, step0, 2 * kMlpMaxIO + 2)) return 1;
     if (N == 0) return 0;
     if (!params || !exp_avg || !exp_avg_sq || !X || !Y || !old_logp || !noise || !perm || !batch_out)
         return fail("dsg_ppo_train_epoch: null argument");
@@ -3514,20 +3487,13 @@ int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg,
     const int bufrows = batch < N ? batch : N;
     const int buf_off = ppo_buf_off(p, bufrows);
     PpoEpochArgs e{params, exp_avg, exp_avg_sq, nullptr, nullptr, X, Y, old_logp, noise, perm, batch_out, N, batch,
-                   (int)(((long long)N + batch - 1) / batch), bufrows, buf_off, lr, beta1, beta2, eps, step0};
+                   (int)(((long long)N + batch - 1) / batch), bufrows, buf_off, {lr, beta1, beta2, eps, step0}};
     const int bytes = (buf_off >= 0 ? buf_off + bufrows * (2 * p.A + 2) : p.lds_floats) * 4;
-    if (mlp_lds_attr(k_ppo_epoch, bytes)) return 1;
     // what does not fit in LDS lives in stream-ordered scratch: the gradient (with the moments in place) and / or the batch buffer
     StreamScratch<float> gws, bws;
     if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
     if (buf_off < 0) { HIPCK(bws.alloc((size_t)R * bufrows * (2 * p.A + 2), s)); e.bufws = bws; }
-    hipLaunchKernelGGL(k_ppo_epoch, dim3((unsigned)R), dim3(kMlpThreads), bytes, s, p, e);
-    const hipError_t launched = hipGetLastError();
-    const hipError_t freed = gws.release(), freed2 = bws.release();
-    HIPCK(launched);
-    HIPCK(freed);
-    HIPCK(freed2);
-    return 0;
+    return baseline_launch(k_ppo_epoch, R, bytes, s, {&gws, &bws}, p, e);
 }
 
 }  // extern "C"

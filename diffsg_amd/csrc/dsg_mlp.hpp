@@ -15,6 +15,8 @@
 // is adam_one of k_adam with the bias corrections formed by the same expressions: the epoch kernel is bit-identical to
 // dsg_mlp_loss_grad + dsg_adam_step per batch (tests/test_gpu_mtfnn.py holds it to that).  The device functions below switch floating-point
 // contraction off: a product and a sum fuse only where fmaf says so, so a function computes the same bits in every kernel it is inlined into.
+// The PPO baseline (dsg_ppo.hpp) is built from the same pieces: the layer functions take the activation (ReLU here, tanh there) as a
+// template argument, and mlp_layer_wgrad, mlp_load_tile, mlp_head_row, mlp_clamp_row, MlpAdam and mlp_adam_step serve both.
 #pragma once
 #include "dsg_kernels.hpp"
 
@@ -37,9 +39,25 @@ struct MlpPlan {
     int lds_floats;             // dynamic LDS of the launch
 };
 
-// a_out[r][j] = (relu)(b[j] + sum_k W[j][k] a_in[r][k]) for the tile's TR rows
+// The activation between the layers, a template argument of the two layer functions that apply it: ReLU (MTFNN) or tanh (PPO).
+constexpr int kMlpRelu = 0, kMlpTanh = 1;
+
+template <int ACT>
+__device__ __forceinline__ float mlp_act(float z) {
+    return ACT == kMlpTanh ? tanhf(z) : (z > 0.f ? z : 0.f);
+}
+
+// d act / d z times g, from the stored activation s = act(z): the ReLU mask, or 1 - s^2.
+template <int ACT>
+__device__ __forceinline__ float mlp_act_bwd(float s, float g) {
+#pragma clang fp contract(off)
+    return ACT == kMlpTanh ? (1.f - s * s) * g : (s > 0.f ? g : 0.f);
+}
+
+// a_out[r][j] = (act)(b[j] + sum_k W[j][k] a_in[r][k]) for the tile's TR rows
+template <int ACT = kMlpRelu>
 __device__ __forceinline__ void mlp_layer_fwd(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ ain, int sin,
-                                              float* __restrict__ aout, int sout, int in, int out, int TR, int tr_shift, bool relu) {
+                                              float* __restrict__ aout, int sout, int in, int out, int TR, int tr_shift, bool act) {
 #pragma clang fp contract(off)
     const int r = threadIdx.x & (TR - 1), jg = threadIdx.x >> tr_shift, NG = kMlpThreads >> tr_shift;
     const float* ar = ain + r * sin;
@@ -51,7 +69,7 @@ __device__ __forceinline__ void mlp_layer_fwd(const float* __restrict__ W, const
             const float x = ar[k];
             a0 = fmaf(w0[k], x, a0); a1 = fmaf(w1[k], x, a1); a2 = fmaf(w2[k], x, a2); a3 = fmaf(w3[k], x, a3);
         }
-        if (relu) { a0 = a0 > 0.f ? a0 : 0.f; a1 = a1 > 0.f ? a1 : 0.f; a2 = a2 > 0.f ? a2 : 0.f; a3 = a3 > 0.f ? a3 : 0.f; }
+        if (act) { a0 = mlp_act<ACT>(a0); a1 = mlp_act<ACT>(a1); a2 = mlp_act<ACT>(a2); a3 = mlp_act<ACT>(a3); }
         float* o = aout + r * sout + jb;
         o[0] = a0;
         if (jb + 1 < out) o[1] = a1;
@@ -117,7 +135,9 @@ __device__ __forceinline__ void mlp_layer_wgrad(const float* __restrict__ delta,
     }
 }
 
-// a_in[r][k] <- (a_in[r][k] > 0) ? sum_j W[j][k] delta[r][j] : 0   (the ReLU in front of this layer; every thread touches its own elements)
+// a_in[r][k] <- act'(a_in[r][k]) * sum_j W[j][k] delta[r][j]   (the activation in front of this layer, from the stored activation; every
+// thread touches its own elements)
+template <int ACT = kMlpRelu>
 __device__ __forceinline__ void mlp_layer_dgrad(const float* __restrict__ W, const float* __restrict__ delta, int sd, float* ain, int sin, int in,
                                                 int out, int TR, int tr_shift) {
 #pragma clang fp contract(off)
@@ -132,12 +152,15 @@ __device__ __forceinline__ void mlp_layer_dgrad(const float* __restrict__ W, con
             a0 = fmaf(wj[kb], dj, a0); a1 = fmaf(wj[k1], dj, a1); a2 = fmaf(wj[k2], dj, a2); a3 = fmaf(wj[k3], dj, a3);
         }
         float* o = ain + r * sin + kb;
-        o[0] = o[0] > 0.f ? a0 : 0.f;
-        if (kb + 1 < in) o[1] = o[1] > 0.f ? a1 : 0.f;
-        if (kb + 2 < in) o[2] = o[2] > 0.f ? a2 : 0.f;
-        if (kb + 3 < in) o[3] = o[3] > 0.f ? a3 : 0.f;
+        o[0] = mlp_act_bwd<ACT>(o[0], a0);
+        if (kb + 1 < in) o[1] = mlp_act_bwd<ACT>(o[1], a1);
+        if (kb + 2 < in) o[2] = mlp_act_bwd<ACT>(o[2], a2);
+        if (kb + 3 < in) o[3] = mlp_act_bwd<ACT>(o[3], a3);
     }
 }
+
+// A row index clamped into [0, N): a permutation entry out of range reads a row of the dataset, never past it.
+__device__ __forceinline__ long long mlp_clamp_row(long long idx, long long N) { return idx < 0 ? 0 : (idx >= N ? N - 1 : idx); }
 
 // Rows [row0, row0 + nrows) of src (through perm, if given; indices clamped into [0, N)) into the tile, the other tile rows zeroed.
 __device__ __forceinline__ void mlp_load_tile(const float* __restrict__ src, const int* __restrict__ perm, long long N, long long row0, int nrows,
@@ -146,9 +169,8 @@ __device__ __forceinline__ void mlp_load_tile(const float* __restrict__ src, con
         const int r = e / width, c = e - r * width;
         float v = 0.f;
         if (r < nrows) {
-            long long idx = perm ? (long long)perm[row0 + r] : row0 + r;
-            idx = idx < 0 ? 0 : (idx >= N ? N - 1 : idx);
-            v = src[(size_t)idx * width + c];
+            const long long idx = perm ? (long long)perm[row0 + r] : row0 + r;
+            v = src[(size_t)mlp_clamp_row(idx, N) * width + c];
         }
         dst[r * stride + c] = v;
     }
@@ -235,6 +257,23 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_loss_grad(MlpPlan p, const 
     mlp_batch_grad(p, wl, wl + p.P, mlp_lds, x, y, nullptr, rows, 0, rows, grad, loss_out);
 }
 
+// Adam's hyper-parameters and the number of steps taken before the epoch: the tail of both epoch kernels' arguments (k_ppo_epoch too).
+struct MlpAdam {
+    double lr, beta1, beta2, eps;
+    long long step0;
+};
+
+// What adam_one needs for step number `step` over P parameters, the bias corrections formed as k_adam forms them.
+struct MlpAdamStep {
+    AdamArgs a;
+    float bias_correction1, bias_correction2_sqrt;
+};
+__device__ __forceinline__ MlpAdamStep mlp_adam_step(int P, MlpAdam h, long long step) {
+    const AdamArgs a{nullptr, nullptr, nullptr, nullptr, (size_t)P, h.lr, h.beta1, h.beta2, 0.0, h.eps, (float)step, 0, nullptr, nullptr};
+    const double bc1 = 1 - pow(a.beta1, (double)a.step), bc2 = 1 - pow(a.beta2, (double)a.step);
+    return {a, (float)bc1, (float)sqrt(bc2)};
+}
+
 struct MlpEpochArgs {
     float* params; float* m; float* v;      // [R][P]
     float* gws;                             // [R][P] gradient workspace when the net's gradient and moments do not fit in LDS, else null
@@ -242,12 +281,11 @@ struct MlpEpochArgs {
     const int* perm;                        // [R][N]
     float* batch_loss;                      // [R][nb]
     int N, batch, nb;
-    double lr, beta1, beta2, eps;
-    long long step0;
+    MlpAdam adam;
 };
 
-// One epoch of one model per workgroup: for every batch mlp_batch_grad, then Adam (adam_one, the bias corrections as k_adam forms them) on the
-// parameters held in LDS.  Parameters (and, where they fit, the moments) are read once and written back once.
+// One epoch of one model per workgroup: for every batch mlp_batch_grad, then Adam (adam_one with mlp_adam_step) on the parameters held in
+// LDS.  Parameters (and, where they fit, the moments) are read once and written back once.
 __global__ __launch_bounds__(kMlpThreads) void k_mlp_epoch(MlpPlan p, MlpEpochArgs e) {
     extern __shared__ float mlp_lds[];
     const int P = p.P;
@@ -267,10 +305,8 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_epoch(MlpPlan p, MlpEpochAr
         const long long row0 = (long long)k * e.batch;
         const int brows = (int)(e.N - row0 < e.batch ? e.N - row0 : e.batch);
         mlp_batch_grad(p, wl, act, mlp_lds, e.X, e.Y, e.perm + rep * e.N, e.N, row0, brows, g, e.batch_loss + rep * e.nb + k);
-        AdamArgs a{nullptr, nullptr, nullptr, nullptr, (size_t)P, e.lr, e.beta1, e.beta2, 0.0, e.eps, (float)(e.step0 + k + 1), 0, nullptr, nullptr};
-        const double bc1 = 1 - pow(a.beta1, (double)a.step), bc2 = 1 - pow(a.beta2, (double)a.step);
-        const float bias_correction1 = (float)bc1, bias_correction2_sqrt = (float)sqrt(bc2);
-        for (int i = threadIdx.x; i < P; i += kMlpThreads) adam_one(wl[i], g[i], m[i], v[i], a, bias_correction1, bias_correction2_sqrt);
+        const MlpAdamStep t = mlp_adam_step(P, e.adam, e.adam.step0 + k + 1);
+        for (int i = threadIdx.x; i < P; i += kMlpThreads) adam_one(wl[i], g[i], m[i], v[i], t.a, t.bias_correction1, t.bias_correction2_sqrt);
         __syncthreads();
     }
     for (int i = threadIdx.x; i < P; i += kMlpThreads) e.params[rep * P + i] = wl[i];

@@ -5,6 +5,8 @@
 //
 // The shape is k_mlp_epoch's (dsg_mlp.hpp): one workgroup (256 threads) owns one model, its parameters sit in LDS for the whole epoch,
 // a batch is walked in tiles of TR rows whose activations (both nets, row stride odd) stay in LDS, weights are wave-uniform broadcasts.
+// Shared with dsg_mlp.hpp, not copied: the layer functions (mlp_layer_fwd / mlp_layer_dgrad with the tanh activation, mlp_layer_wgrad),
+// mlp_load_tile, mlp_head_row, the row clamp, and Adam's arguments and bias corrections (MlpAdam, mlp_adam_step).
 // A batch takes three passes, because the NU decoder needs the (min, max) of the WHOLE batch's softmaxed actions before any reward exists:
 //   pass 1  per tile: forward of both nets; per row: a = noise * std + mu, new_logp, softmax(a), value  -> the batch buffer
 //   pass 2  NU: workgroup-wide (min, max) of the buffer's columns 0, 1; per tile: X / Y rows again, one thread per row: reward, then the
@@ -44,57 +46,13 @@ struct PpoPlan {
     float lo, span, W, width, height, p_sum;        // scaler_min, (float)(scaler_max - scaler_min), W | NU's area and power
 };
 
-__device__ __forceinline__ void ppo_layer_fwd(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ ain, int sin,
-                                              float* __restrict__ aout, int sout, int in, int out, int TR, int tr_shift, bool act) {
-#pragma clang fp contract(off)
-    const int r = threadIdx.x & (TR - 1), jg = threadIdx.x >> tr_shift, NG = kMlpThreads >> tr_shift;
-    const float* ar = ain + r * sin;
-    for (int jb = 4 * jg; jb < out; jb += 4 * NG) {
-        const int j1 = min(jb + 1, out - 1), j2 = min(jb + 2, out - 1), j3 = min(jb + 3, out - 1);      // clamped: read, not stored
-        const float *w0 = W + jb * in, *w1 = W + j1 * in, *w2 = W + j2 * in, *w3 = W + j3 * in;
-        float a0 = b[jb], a1 = b[j1], a2 = b[j2], a3 = b[j3];
-        for (int k = 0; k < in; ++k) {
-            const float x = ar[k];
-            a0 = fmaf(w0[k], x, a0); a1 = fmaf(w1[k], x, a1); a2 = fmaf(w2[k], x, a2); a3 = fmaf(w3[k], x, a3);
-        }
-        if (act) { a0 = tanhf(a0); a1 = tanhf(a1); a2 = tanhf(a2); a3 = tanhf(a3); }
-        float* o = aout + r * sout + jb;
-        o[0] = a0;
-        if (jb + 1 < out) o[1] = a1;
-        if (jb + 2 < out) o[2] = a2;
-        if (jb + 3 < out) o[3] = a3;
-    }
-}
-
-// a_in[r][k] <- (1 - a_in[r][k]^2) * sum_j W[j][k] delta[r][j]   (the tanh in front of this layer, from the stored activation)
-__device__ __forceinline__ void ppo_layer_dgrad(const float* __restrict__ W, const float* __restrict__ delta, int sd, float* ain, int sin, int in,
-                                                int out, int TR, int tr_shift) {
-#pragma clang fp contract(off)
-    const int r = threadIdx.x & (TR - 1), kg = threadIdx.x >> tr_shift, NG = kMlpThreads >> tr_shift;
-    const float* d = delta + r * sd;
-    for (int kb = 4 * kg; kb < in; kb += 4 * NG) {
-        const int k1 = min(kb + 1, in - 1), k2 = min(kb + 2, in - 1), k3 = min(kb + 3, in - 1);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        for (int j = 0; j < out; ++j) {
-            const float dj = d[j];
-            const float* wj = W + j * in;
-            a0 = fmaf(wj[kb], dj, a0); a1 = fmaf(wj[k1], dj, a1); a2 = fmaf(wj[k2], dj, a2); a3 = fmaf(wj[k3], dj, a3);
-        }
-        float* o = ain + r * sin + kb;
-        o[0] = (1.f - o[0] * o[0]) * a0;
-        if (kb + 1 < in) o[1] = (1.f - o[1] * o[1]) * a1;
-        if (kb + 2 < in) o[2] = (1.f - o[2] * o[2]) * a2;
-        if (kb + 3 < in) o[3] = (1.f - o[3] * o[3]) * a3;
-    }
-}
-
 // Both nets on the tile whose states are in place: layer l of the critic and of the actor, then one barrier.
 __device__ __forceinline__ void ppo_tile_forward(const PpoPlan& p, const float* __restrict__ wl, float* __restrict__ act) {
     for (int l = 0; l < 4; ++l) {
 #pragma unroll
         for (int n = 0; n < 2; ++n)
-            ppo_layer_fwd(wl + p.woff[n][l], wl + p.boff[n][l], act + p.aoff[n][l], p.astr[n][l], act + p.aoff[n][l + 1], p.astr[n][l + 1], p.w[n][l],
-                          p.w[n][l + 1], p.TR, p.tr_shift, l < 3);
+            mlp_layer_fwd<kMlpTanh>(wl + p.woff[n][l], wl + p.boff[n][l], act + p.aoff[n][l], p.astr[n][l], act + p.aoff[n][l + 1], p.astr[n][l + 1],
+                                    p.w[n][l], p.w[n][l + 1], p.TR, p.tr_shift, l < 3);
         __syncthreads();
     }
 }
@@ -102,7 +60,7 @@ __device__ __forceinline__ void ppo_tile_forward(const PpoPlan& p, const float* 
 // The dataset row of position pos (through perm, if given), clamped into [0, N).
 __device__ __forceinline__ long long ppo_row(const int* __restrict__ perm, long long N, long long pos) {
     const long long idx = perm ? (long long)perm[pos] : pos;
-    return idx < 0 ? 0 : (idx >= N ? N - 1 : idx);
+    return mlp_clamp_row(idx, N);
 }
 
 constexpr float kPpoLogSqrt2Pi = (float)0.9189385332046727;     // math.log(math.sqrt(2 * math.pi))
@@ -294,8 +252,8 @@ __device__ __forceinline__ void ppo_batch(const PpoPlan& p, const float* __restr
             if (l > 0) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
-                    ppo_layer_dgrad(wl + p.woff[n][l], act + p.aoff[n][l + 1], p.astr[n][l + 1], act + p.aoff[n][l], p.astr[n][l], p.w[n][l],
-                                    p.w[n][l + 1], TR, p.tr_shift);
+                    mlp_layer_dgrad<kMlpTanh>(wl + p.woff[n][l], act + p.aoff[n][l + 1], p.astr[n][l + 1], act + p.aoff[n][l], p.astr[n][l],
+                                              p.w[n][l], p.w[n][l + 1], TR, p.tr_shift);
                 __syncthreads();
             }
         }
@@ -360,12 +318,11 @@ struct PpoEpochArgs {
     const int* perm;                        // [R][N]
     float* batch_out;                       // [R][nb][3]
     int N, batch, nb, bufrows, buf_off;
-    double lr, beta1, beta2, eps;
-    long long step0;
+    MlpAdam adam;
 };
 
-// One epoch of one agent per workgroup: for every batch ppo_batch, then Adam (adam_one, the bias corrections as k_adam forms them) over
-// the critic and actor range of the parameters held in LDS.
+// One epoch of one agent per workgroup: for every batch ppo_batch, then Adam (adam_one with mlp_adam_step) over the critic and actor range
+// of the parameters held in LDS.
 __global__ __launch_bounds__(kMlpThreads) void k_ppo_epoch(PpoPlan p, PpoEpochArgs e) {
     extern __shared__ float ppo_lds[];
     const int P = p.P, A = p.A;
@@ -388,10 +345,8 @@ __global__ __launch_bounds__(kMlpThreads) void k_ppo_epoch(PpoPlan p, PpoEpochAr
         const long long row0 = (long long)k * e.batch;
         const int brows = (int)(e.N - row0 < e.batch ? e.N - row0 : e.batch);
         ppo_batch(p, wl, act, ppo_lds, buf, io, row0, brows, g, e.batch_out + (rep * e.nb + k) * 3);
-        AdamArgs a{nullptr, nullptr, nullptr, nullptr, (size_t)P, e.lr, e.beta1, e.beta2, 0.0, e.eps, (float)(e.step0 + k + 1), 0, nullptr, nullptr};
-        const double bc1 = 1 - pow(a.beta1, (double)a.step), bc2 = 1 - pow(a.beta2, (double)a.step);
-        const float bias_correction1 = (float)bc1, bias_correction2_sqrt = (float)sqrt(bc2);
-        for (int i = A + threadIdx.x; i < P; i += kMlpThreads) adam_one(wl[i], g[i], m[i], v[i], a, bias_correction1, bias_correction2_sqrt);
+        const MlpAdamStep t = mlp_adam_step(P, e.adam, e.adam.step0 + k + 1);
+        for (int i = A + threadIdx.x; i < P; i += kMlpThreads) adam_one(wl[i], g[i], m[i], v[i], t.a, t.bias_correction1, t.bias_correction2_sqrt);
         __syncthreads();
     }
     for (int i = A + threadIdx.x; i < P; i += kMlpThreads) e.params[rep * P + i] = wl[i];

@@ -11,16 +11,20 @@ Reference quirk kept and named: the reference's evaluation loader shuffles too (
 are scored against inputs and labels in a different row order.  The drivers return both figures: `*_reference_order`
 follows that loop (and consumes torch's global generator as it does), `*_aligned` scores row against row.
 """
-from collections import Counter, OrderedDict
+from collections import OrderedDict
 import ctypes
+from functools import partial
 
-import numpy as np
 import torch
 import torch.nn as nn
-import torch.utils.data as data
 
 from . import _lib
+from . import _smallnet as _sn
+from ._smallnet import epoch_lrs, epoch_permutation, flat_params  # noqa: F401  (part of this module's interface)
 from .diffusion import init_weights
+
+_cuda = partial(_sn.cuda, "mtfnn")
+_call = _sn.call
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -116,35 +120,6 @@ def model_desc(model):
     return mlp_desc([lins[0].in_features] + [l.out_features for l in lins], model.n_sig)
 
 
-def flat_params(model):
-    """The parameters as one flat float32 vector in state-dict order (lin1.weight, lin1.bias, lin2.weight, ...)."""
-    return torch.cat([p.detach().reshape(-1) for p in model.parameters()]).to(torch.float32).contiguous()
-
-
-def _unflatten_into(model, flat):
-    off = 0
-    with torch.no_grad():
-        for p in model.parameters():
-            p.copy_(flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-
-
-def _cuda(t, device, what):
-    if not torch.is_tensor(t):
-        t = torch.as_tensor(np.asarray(t))
-    t = t.detach().to(device=device, dtype=torch.float32).contiguous()
-    if not t.is_cuda:
-        raise RuntimeError(f"diffsg_amd.mtfnn.{what}: tensors are not on a HIP device; libdiffsg_hip has no CPU path")
-    if t.dim() != 2:
-        raise ValueError(f"{what}: expected a (rows, columns) tensor, got {tuple(t.shape)}")
-    return t
-
-
-def _call(name, dev, *args):
-    with torch.cuda.device(dev):
-        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr()))
-
-
 def forward_flat(desc, params, x):
     """dsg_mlp_forward on a flat parameter vector."""
     out = torch.empty((x.shape[0], desc.widths[desc.n_layers]), device=x.device, dtype=torch.float32)
@@ -152,20 +127,9 @@ def forward_flat(desc, params, x):
     return out
 
 
-def _cached_flat(model):
-    """(descriptor, flat parameters), rebuilt only after a parameter changed (in-place writes bump a tensor's version, a move to another
-    device changes its address): a repeated no-grad forward is then the library launch alone."""
-    key = tuple((p.data_ptr(), p._version) for p in model.parameters())
-    hit = model.__dict__.get("_dsg_flat")
-    if hit is None or hit[0] != key:
-        hit = (key, model_desc(model), flat_params(model))
-        model.__dict__["_dsg_flat"] = hit
-    return hit[1], hit[2]
-
-
 def device_forward(model, x):
     x = _cuda(x, x.device, "forward")
-    desc, flat = _cached_flat(model)
+    desc, flat = _sn.cached_flat(model, model_desc)
     if x.shape[1] != desc.widths[0]:
         raise ValueError(f"forward: x has {x.shape[1]} columns, the net {desc.widths[0]} inputs")
     return forward_flat(desc, flat, x)
@@ -188,52 +152,12 @@ def loss_grad(model, x, y):
     if x.shape[1] != desc.widths[0] or y.shape != (x.shape[0], desc.widths[desc.n_layers]):
         raise ValueError(f"loss_grad: x {tuple(x.shape)} / y {tuple(y.shape)} do not fit the net")
     loss, flat = loss_grad_flat(desc, flat_params(model), x, y)
-    grads, off = {}, 0
-    for name, p in model.named_parameters():
-        grads[name] = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-    return loss, grads
+    return loss, _sn.named_grads(model, flat)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # training
 # ---------------------------------------------------------------------------------------------------------------------
-def epoch_lrs(lr, milestones, epochs, gamma=0.1):
-    """The learning rate of every epoch as torch's MultiStepLR yields it: multiplied by gamma ** (times the epoch is listed) when
-    the epoch count reaches a milestone -- the chained products, not lr * gamma ** k, so the doubles are the scheduler's."""
-    count = Counter(milestones)
-    out, cur = [], float(lr)
-    for e in range(epochs):
-        if e in count:
-            cur = cur * gamma ** count[e]
-        out.append(cur)
-    return out
-
-
-class _Indices(data.Dataset):
-    """arange(n) as a dataset that hands a batch of indices back in one call (the loader's sampler and generator use are those of a
-    DataLoader over TensorDataset(arange(n)); only the per-sample fetch, 40 000 tensor reads per epoch, is left out)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        return i
-
-    def __getitems__(self, idx):
-        return idx
-
-
-def epoch_permutation(n, batch_size):
-    """The row order of one epoch: a shuffling DataLoader iterated once, as the reference's `for x, y in data_loader` does, so torch's
-    global generator is consumed exactly as there (the iterator's base seed, then the sampler's seed)."""
-    loader = data.DataLoader(_Indices(n), batch_size=batch_size, shuffle=True, collate_fn=torch.as_tensor)
-    return torch.cat(list(loader)) if n else torch.empty(0, dtype=torch.int64)
-
-
 def train_epoch_flat(desc, params, exp_avg, exp_avg_sq, X, Y, perm, batch, lr, step0, betas=(0.9, 0.999), eps=1e-8):
     """dsg_mlp_train_epoch on flat [R][P] tensors (updated in place); perm int32 [R][N].  Returns batch_loss [R][ceil(N / batch)]."""
     R, N = perm.shape
@@ -250,17 +174,9 @@ def fit(model, X, Y, epochs, batch_size=512, lr=0.005, milestones=(20,), replica
     same launches (all of `model`'s architecture, `model` among them), each with permutations of its
     own, drawn replica by replica within each epoch.  Returns the per-epoch log values, [epochs][R] (the reference's
     `epoch_loss / epoch_sample_num`: the sum of the batch means over the row count)."""
-    models = list(replicas) if replicas else [model]
-    if not any(m is model for m in models):
-        raise ValueError("fit: `replicas` is the whole list of models to train and must contain `model`")
     dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("diffsg_amd.mtfnn.fit: the model is not on a HIP device; libdiffsg_hip has no CPU path")
+    models = _sn.replica_list("mtfnn", "model", model, replicas, dev, model_desc)
     desc = model_desc(model)
-    for m in models:
-        d = model_desc(m)
-        if list(d.widths) != list(desc.widths) or d.n_layers != desc.n_layers or d.n_sig != desc.n_sig:
-            raise ValueError("fit: the replicas are not of one architecture")
     X, Y = _cuda(X, dev, "fit"), _cuda(Y, dev, "fit")
     N = X.shape[0]
     if X.shape[1] != desc.widths[0] or Y.shape != (N, desc.widths[desc.n_layers]):
@@ -272,29 +188,18 @@ def fit(model, X, Y, epochs, batch_size=512, lr=0.005, milestones=(20,), replica
     for epoch, cur_lr in enumerate(epoch_lrs(lr, milestones, epochs)):
         perm = torch.stack([epoch_permutation(N, batch_size) for _ in models]).to(device=dev, dtype=torch.int32)
         bl = train_epoch_flat(desc, params, exp_avg, exp_avg_sq, X, Y, perm, batch_size, cur_lr, epoch * nb).cpu()
-        vals = []
-        for r in range(len(models)):
-            epoch_loss = 0
-            for v in bl[r].tolist():           # the reference's running sum of loss.item()
-                epoch_loss += v
-            vals.append(epoch_loss / N if N else 0.0)
+        vals = [_sn.running_sum(row) / N if N else 0.0 for row in bl.tolist()]
         history.append(vals)
         if log is not None:
             log(f"Epoch: {epoch}, Loss: {vals[0] if len(vals) == 1 else vals}")
     for m, p in zip(models, params):
-        _unflatten_into(m, p)
+        _sn.unflatten_into(m, p)
     return history
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # drivers
 # ---------------------------------------------------------------------------------------------------------------------
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: this build of DiffSG has no CPU path")
-    return torch.device("cuda:0")
-
-
 def _predict(model, X_test, batch_size=512):
     """(predictions row for row, predictions in the reference's evaluation order).  The reference's evaluation loader shuffles
     (MTFNN.py:77): its Y_pred is model(X_test[perm]); the permutation is drawn as that loader draws it."""
@@ -304,26 +209,13 @@ def _predict(model, X_test, batch_size=512):
     return aligned, aligned[perm]
 
 
-def _figures(pred, true, tag, out):
-    out[f"sum_ratio_{tag}"] = float(torch.sum(pred) / torch.sum(true))
-    out[f"mean_diff_{tag}"] = float(torch.mean(pred - true))
-
-
-def _finish(model, out, save_path, log):
-    if save_path is not None:
-        torch.save(model.state_dict(), save_path)
-    if log is not None:
-        log(", ".join(f"{k}: {v}" for k, v in out.items() if not k.startswith("history")))
-    return model, out
-
-
 def mtfnn_co(dataset_path, epochs=50, batch_size=512, lr=0.005, milestones=(20,), replicas=None, save_path=None, log=print):
     """mtfnn_co, MTFNN.py:29-104.  Returns (model, {"sum_ratio_*": the reference's "exceeded ratio", "mean_diff_*": its "avg cost
     diff"}); `replicas`: further co_net models to train beside it (fit)."""
     from . import decode
     from .classifier_free_CO import co_data_load
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
-    dev = _device()
+    dev = _sn.device()
     node_num = Y_train.shape[1]
     model = co_net(node_num * 3, node_num)
     model.apply(init_weights)
@@ -334,9 +226,9 @@ def mtfnn_co(dataset_path, epochs=50, batch_size=512, lr=0.005, milestones=(20,)
     lo, hi = custom_config['scaler_min'], custom_config['scaler_max']
     X_raw = X_t * (hi - lo) + lo
     true_cost = decode.co_cost(X_raw, Y_t)
-    _figures(decode.co_cost(X_raw, ref_order), true_cost, "reference_order", out)
-    _figures(decode.co_cost(X_raw, aligned), true_cost, "aligned", out)
-    return _finish(model, out, save_path, log)
+    _sn.figures(decode.co_cost(X_raw, ref_order), true_cost, "reference_order", out)
+    _sn.figures(decode.co_cost(X_raw, aligned), true_cost, "aligned", out)
+    return _sn.finish(model, out, save_path, log)
 
 
 def mtfnn_msr(dataset_path, epochs=50, batch_size=512, lr=0.005, milestones=(20,), replicas=None, save_path=None, log=print):
@@ -347,7 +239,7 @@ def mtfnn_msr(dataset_path, epochs=50, batch_size=512, lr=0.005, milestones=(20,
     X_train, Y_train, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     Y_train /= W  # Softmax train (in place, as the reference)
-    dev = _device()
+    dev = _sn.device()
     model = msr_net(M, M)
     model.apply(init_weights)
     model.to(dev)
@@ -358,9 +250,9 @@ def mtfnn_msr(dataset_path, epochs=50, batch_size=512, lr=0.005, milestones=(20,
     lo, hi = custom_config['scaler_min'], custom_config['scaler_max']
     X_raw = X_t * (hi - lo) + lo
     true_rate = decode.msr_rate(Y_t, X_raw)
-    _figures(decode.msr_rate(ref_order, X_raw), true_rate, "reference_order", out)
-    _figures(decode.msr_rate(aligned, X_raw), true_rate, "aligned", out)
-    return _finish(model, out, save_path, log)
+    _sn.figures(decode.msr_rate(ref_order, X_raw), true_rate, "reference_order", out)
+    _sn.figures(decode.msr_rate(aligned, X_raw), true_rate, "aligned", out)
+    return _sn.finish(model, out, save_path, log)
 
 
 def mtfnn_nu(dataset_path, epochs=100, width=400, height=400, batch_size=512, lr=0.005, milestones=(20, 60), replicas=None,
@@ -371,7 +263,7 @@ def mtfnn_nu(dataset_path, epochs=100, width=400, height=400, batch_size=512, lr
     from .classifier_free_NU import nu_data_load
     X_train, Y_train, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
-    dev = _device()
+    dev = _sn.device()
     model = MTFNN(K * 2, 2 + K)
     model.apply(init_weights)
     model.to(dev)
@@ -382,6 +274,6 @@ def mtfnn_nu(dataset_path, epochs=100, width=400, height=400, batch_size=512, lr
     ys = torch.tensor([width, height] + [P_sum] * K, device=dev, dtype=torch.float32)
     X_raw = X_t * xs
     true_rate = decode.nu_rate(Y_t * ys, X_raw)
-    _figures(decode.nu_rate(ref_order * ys, X_raw), true_rate, "reference_order", out)
-    _figures(decode.nu_rate(aligned * ys, X_raw), true_rate, "aligned", out)
-    return _finish(model, out, save_path, log)
+    _sn.figures(decode.nu_rate(ref_order * ys, X_raw), true_rate, "reference_order", out)
+    _sn.figures(decode.nu_rate(aligned * ys, X_raw), true_rate, "aligned", out)
+    return _sn.finish(model, out, save_path, log)

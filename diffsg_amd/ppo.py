@@ -16,6 +16,7 @@ per-batch `Normal.sample()` on its own device: equality with a reference run fro
 noise fed in is, and the tests hold `dsg_ppo_loss_grad` / `dsg_ppo_train_epoch` to it.
 """
 import ctypes
+from functools import partial
 
 import numpy as np
 import torch
@@ -23,7 +24,11 @@ import torch.nn as nn
 from torch.distributions import Normal
 
 from . import _lib
-from .mtfnn import _call, _cuda, _device, _figures, _finish, epoch_lrs, epoch_permutation
+from . import _smallnet as _sn
+from ._smallnet import epoch_lrs, epoch_permutation, flat_params  # noqa: F401  (part of this module's interface)
+
+_cuda = partial(_sn.cuda, "ppo")
+_call = _sn.call
 
 ENVS = {"co": 0, "msr": 1, "nu": 2}
 HIDDEN = (64, 16, 32)
@@ -94,19 +99,6 @@ def agent_desc(agent, env_config=None):
     return ppo_desc(agent.state_dim, agent.action_dim, (env_config or {}).get("env"), env_config, hidden)
 
 
-def flat_params(agent):
-    """The parameters as one flat float32 vector in state-dict order (log_std, critic.0.weight, ..., actor.6.bias)."""
-    return torch.cat([p.detach().reshape(-1) for p in agent.parameters()]).to(torch.float32).contiguous()
-
-
-def _unflatten_into(agent, flat):
-    off = 0
-    with torch.no_grad():
-        for p in agent.parameters():
-            p.copy_(flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-
-
 def forward_flat(desc, params, x):
     """dsg_ppo_forward on a flat parameter vector: (mu [rows][A], value [rows])."""
     mu = torch.empty((x.shape[0], desc.action_dim), device=x.device, dtype=torch.float32)
@@ -115,19 +107,9 @@ def forward_flat(desc, params, x):
     return mu, value
 
 
-def _cached_flat(agent):
-    """(descriptor, flat parameters), rebuilt only after a parameter's version or address changed, as mtfnn._cached_flat."""
-    key = tuple((p.data_ptr(), p._version) for p in agent.parameters())
-    hit = agent.__dict__.get("_dsg_flat")
-    if hit is None or hit[0] != key:
-        hit = (key, agent_desc(agent), flat_params(agent))
-        agent.__dict__["_dsg_flat"] = hit
-    return hit[1], hit[2]
-
-
 def device_forward(agent, x):
     x = _cuda(x, x.device, "forward")
-    desc, flat = _cached_flat(agent)
+    desc, flat = _sn.cached_flat(agent, agent_desc)
     if x.shape[1] != desc.state_dim:
         raise ValueError(f"forward: x has {x.shape[1]} columns, the agent {desc.state_dim} state inputs")
     return forward_flat(desc, flat, x)
@@ -157,11 +139,7 @@ def loss_grad(agent, x, y, old_logp, noise, env_config):
         raise ValueError(f"loss_grad: x {tuple(x.shape)} / y {tuple(y.shape)} / old_logp {tuple(old_logp.shape)} / noise "
                          f"{tuple(noise.shape)} do not fit the agent")
     out3, new_logp, reward, flat = loss_grad_flat(desc, flat_params(agent), x, y, old_logp, noise)
-    grads, off = {}, 0
-    for name, p in agent.named_parameters():
-        grads[name] = flat[off:off + p.numel()].view_as(p)
-        off += p.numel()
-    return out3, new_logp, reward, grads
+    return out3, new_logp, reward, _sn.named_grads(agent, flat)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -190,20 +168,12 @@ def fit(agent, X, Y, env_config, epochs, batch_size=512, lr=0.005, milestones=(2
     sweep over the critic and actor range), MultiStepLR(gamma=0.1), one launch per epoch.  env_config: the data loader's custom_config
     plus "env": "co" | "msr" | "nu".  X, Y (arrays or tensors) are uploaded once.  `replicas`: the list of agents trained side by side
     in the same launches (`agent` among them), each with old log-probabilities, permutations and noise of its own.  Per epoch: the
-    permutations (mtfnn.epoch_permutation, composed with the previous epoch's visiting order, so that `perm` and `old_logp` are in
+    permutations (epoch_permutation, composed with the previous epoch's visiting order, so that `perm` and `old_logp` are in
     dataset-row terms), one torch.randn on the device, one launch, one read-back.  Returns the per-epoch log values,
     [epochs][R] of (actor loss, critic loss, reward): the reference's sums of batch means over the row count, and reward per row."""
-    agents = list(replicas) if replicas else [agent]
-    if not any(a is agent for a in agents):
-        raise ValueError("fit: `replicas` is the whole list of agents to train and must contain `agent`")
     dev = agent.log_std.device
-    if dev.type != "cuda":
-        raise RuntimeError("diffsg_amd.ppo.fit: the agent is not on a HIP device; libdiffsg_hip has no CPU path")
+    agents = _sn.replica_list("ppo", "agent", agent, replicas, dev, partial(agent_desc, env_config=env_config))
     desc = agent_desc(agent, env_config)
-    for a in agents:
-        d = agent_desc(a, env_config)
-        if (d.state_dim, d.action_dim, list(d.hidden)) != (desc.state_dim, desc.action_dim, list(desc.hidden)):
-            raise ValueError("fit: the replicas are not of one architecture")
     X, Y = _cuda(X, dev, "fit"), _cuda(Y, dev, "fit")
     N, A, R = X.shape[0], desc.action_dim, len(agents)
     if X.shape[1] != desc.state_dim or Y.shape != (N, A):
@@ -221,20 +191,14 @@ def fit(agent, X, Y, env_config, epochs, batch_size=512, lr=0.005, milestones=(2
         perm = torch.stack(visited).to(device=dev, dtype=torch.int32)
         noise = torch.randn((R, N, A), device=dev, dtype=torch.float32)
         bo = train_epoch_flat(desc, params, exp_avg, exp_avg_sq, X, Y, old_logp, noise, perm, batch_size, cur_lr, epoch * nb).cpu()
-        vals = []
-        for r in range(R):
-            epoch_a_loss, epoch_c_loss, epoch_reward = 0, 0, 0
-            for a_loss, c_loss, rew in bo[r].tolist():      # the reference's running sums of .item()
-                epoch_a_loss += a_loss
-                epoch_c_loss += c_loss
-                epoch_reward += rew
-            vals.append((epoch_a_loss / N, epoch_c_loss / N, epoch_reward / N) if N else (0.0, 0.0, 0.0))
+        # per replica the running sums of actor loss, critic loss and reward over the batches
+        vals = [tuple(_sn.running_sum(col) / N for col in zip(*rows)) if N else (0.0, 0.0, 0.0) for rows in bo.tolist()]
         history.append(vals)
         if log is not None:
             log(f"Epoch: {epoch}, Actor loss: {vals[0][0]}, Critic loss: {vals[0][1]}.")
             log(f"Reward: {vals[0][2]}")
     for a, p in zip(agents, params):
-        _unflatten_into(a, p)
+        _sn.unflatten_into(a, p)
     return history
 
 
@@ -263,7 +227,7 @@ def ppo_co(dataset_path, epochs=200, batch_size=512, lr=0.005, milestones=(20, 1
     from . import decode
     from .classifier_free_CO import co_data_load
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
-    dev = _device()
+    dev = _sn.device()
     node_num = Y_train.shape[1]
     agent = PPOAgent(node_num * 3, node_num).to(dev)
     out = _train(agent, X_train, Y_train, dict(custom_config, env="co"), epochs, batch_size, lr, milestones, replicas, log)
@@ -274,9 +238,9 @@ def ppo_co(dataset_path, epochs=200, batch_size=512, lr=0.005, milestones=(20, 1
     lo, hi = custom_config['scaler_min'], custom_config['scaler_max']
     X_raw = X_t * (hi - lo) + lo
     true_cost = decode.co_cost(X_raw, Y_t)
-    _figures(decode.co_cost(X_raw, ref_order), true_cost, "reference_order", out)
-    _figures(decode.co_cost(X_raw, aligned), true_cost, "aligned", out)
-    return _finish(agent, out, save_path, log)
+    _sn.figures(decode.co_cost(X_raw, ref_order), true_cost, "reference_order", out)
+    _sn.figures(decode.co_cost(X_raw, aligned), true_cost, "aligned", out)
+    return _sn.finish(agent, out, save_path, log)
 
 
 def ppo_msr(dataset_path, epochs=100, batch_size=512, lr=0.005, milestones=(20,), replicas=None, save_path=None, log=print):
@@ -287,7 +251,7 @@ def ppo_msr(dataset_path, epochs=100, batch_size=512, lr=0.005, milestones=(20,)
     X_train, Y_train, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     Y_train /= W
-    dev = _device()
+    dev = _sn.device()
     agent = PPOAgent(M, M).to(dev)
     out = _train(agent, X_train, Y_train, dict(custom_config, env="msr"), epochs, batch_size, lr, milestones, replicas, log)
     X_t, Y_t = _cuda(X_test, dev, "ppo_msr"), _cuda(Y_test, dev, "ppo_msr")
@@ -297,9 +261,9 @@ def ppo_msr(dataset_path, epochs=100, batch_size=512, lr=0.005, milestones=(20,)
     lo, hi = custom_config['scaler_min'], custom_config['scaler_max']
     X_raw = X_t * (hi - lo) + lo
     true_rate = decode.msr_rate(Y_t, X_raw)
-    _figures(decode.msr_rate(ref_order, X_raw), true_rate, "reference_order", out)
-    _figures(decode.msr_rate(aligned, X_raw), true_rate, "aligned", out)
-    return _finish(agent, out, save_path, log)
+    _sn.figures(decode.msr_rate(ref_order, X_raw), true_rate, "reference_order", out)
+    _sn.figures(decode.msr_rate(aligned, X_raw), true_rate, "aligned", out)
+    return _sn.finish(agent, out, save_path, log)
 
 
 def ppo_nu(dataset_path, epochs=50, width=400, height=400, batch_size=512, lr=0.005, milestones=(20,), replicas=None, save_path=None,
@@ -314,7 +278,7 @@ def ppo_nu(dataset_path, epochs=50, width=400, height=400, batch_size=512, lr=0.
     Y_train[:, 1] *= height
     K, P_sum = custom_config['K'], custom_config['P_sum']
     Y_train[:, -K:] *= P_sum
-    dev = _device()
+    dev = _sn.device()
     agent = PPOAgent(K * 2, K + 2).to(dev)
     cfg = dict(custom_config, env="nu", width=width, height=height)
     out = _train(agent, X_train, Y_train, cfg, epochs, batch_size, lr, milestones, replicas, log)
@@ -326,5 +290,5 @@ def ppo_nu(dataset_path, epochs=50, width=400, height=400, batch_size=512, lr=0.
     true_rate = decode.nu_rate(Y_t * ys, X_raw)
     for tag, batches in zip(("aligned", "reference_order"), _orders(X_t.shape[0], batch_size, dev)):
         pred = torch.cat([decode.nu_decode(mean[idx].contiguous(), width, height, P_sum) for idx in batches])
-        _figures(decode.nu_rate(pred, X_raw), true_rate, tag, out)
-    return _finish(agent, out, save_path, log)
+        _sn.figures(decode.nu_rate(pred, X_raw), true_rate, tag, out)
+    return _sn.finish(agent, out, save_path, log)

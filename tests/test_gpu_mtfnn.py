@@ -19,6 +19,9 @@ TOL = 1e-5      # forward: max|a - b| / max|b|, the bar tests/test_gpu_parity.py
 GTOL = 1e-4     # gradients, per tensor on the grad_errs scale
 ATOL = 1e-3     # parameters after three Adam steps (rel), the bar of the project's three-step Adam test
 NU32 = ((64, 64, 32, 16, 32, 34), 2)        # the NU net at K = 32: gradient and moments do not fit in LDS beside it (global-memory form)
+# nets near the width limits, where the tile is lower than 64 rows (both keep gradient and moments in global memory)
+WIDE = {"wide32": ((128, 64, 64, 128), 64),                 # P = 20 736, TR = 32
+        "wide16": ((128, 64, 64, 64, 64, 128), 0)}          # P = 29 056, TR = 16
 
 
 @pytest.fixture(scope="module")
@@ -108,6 +111,20 @@ def test_loss_and_gradients_against_goldens(g14, case, tag):
     assert max(errs.values()) < GTOL, errs
 
 
+@pytest.mark.parametrize("case", list(WIDE))
+def test_forward_of_the_low_tile_nets(case):
+    """Tiles of 32 and of 16 rows against the float64 restatement; a float32 emulation of the two nets (k in order, no FMA) is
+    1.5e-7 and 3.0e-7 away from it.  Measured on an MI355X: 1.19e-07 (wide32) and 5.12e-07 (wide16); the bar is 1e-5."""
+    from diffsg_amd.mtfnn import forward_flat
+    widths, n_sig = WIDE[case]
+    w, X, _ = synth_case(widths, 42, 0.1)
+    got = forward_flat(desc_of(widths, n_sig), dev(MR.flat(w, widths)), dev(X))
+    err = rel(got, MR.forward(w, widths, n_sig, X))
+    print(f"forward {case} rows {MR.ROWS}: {err:.2e}")
+    assert got.shape == (MR.ROWS, widths[-1])
+    assert err < TOL
+
+
 def compose(desc, p0, X, Y, perm, batch, step0=0, lr=MR.LR):
     """The epoch from dsg_mlp_loss_grad + dsg_adam_step, one batch at a time, on the gathered rows."""
     from diffsg_amd.mtfnn import loss_grad_flat
@@ -121,13 +138,21 @@ def compose(desc, p0, X, Y, perm, batch, step0=0, lr=MR.LR):
     return p, m, v, torch.stack(losses)
 
 
+def synth_case(widths, seed, std):
+    """(weights, X, Y): N(0, std^2) weights and uniform inputs and targets, seeded."""
+    rs = np.random.RandomState(seed)
+    X, Y = rs.uniform(0, 1, (MR.ROWS, widths[0])).astype(np.float32), rs.uniform(0, 1, (MR.ROWS, widths[-1])).astype(np.float32)
+    return MR.synth_state(widths, seed, std), X, Y
+
+
 def shaped_case(g14, case):
-    """(desc, flat trained-like parameters, X, Y) of a golden case, or of the K = 32 NU net on seeded inputs."""
+    """(desc, flat trained-like parameters, X, Y) of a golden case, or of the K = 32 NU net / a wide net on seeded inputs."""
     if case == "nu32":
         widths, n_sig = NU32
-        rs = np.random.RandomState(32)
-        X, Y = rs.uniform(0, 1, (MR.ROWS, widths[0])).astype(np.float32), rs.uniform(0, 1, (MR.ROWS, widths[-1])).astype(np.float32)
-        w = MR.synth_state(widths, 32)
+        w, X, Y = synth_case(widths, 32, 0.3)
+    elif case in WIDE:
+        widths, n_sig = WIDE[case]
+        w, X, Y = synth_case(widths, 42, 0.1)
     else:
         widths, n_sig = MR.CASES[case]
         X, Y = MR.inputs(case)
@@ -136,7 +161,7 @@ def shaped_case(g14, case):
 
 
 @pytest.mark.parametrize("batch", [64, 104, 512])
-@pytest.mark.parametrize("case", ["co3", "msr80", "nu3", "nu32"])
+@pytest.mark.parametrize("case", ["co3", "msr80", "nu3", "nu32", "wide32", "wide16"])
 def test_epoch_is_the_composition_bit_for_bit(g14, case, batch):
     from diffsg_amd.mtfnn import train_epoch_flat
     desc, p0, X, Y = shaped_case(g14, case)

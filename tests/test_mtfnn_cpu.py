@@ -1,5 +1,6 @@
 """MTFNN baseline, host side (no GPU): the float64 restatement against the torch goldens, the modules' layout and seeded
 initialisation, the per-epoch learning rates, and the permutations `fit` trains on."""
+import ctypes
 import os
 
 import numpy as np
@@ -150,3 +151,47 @@ def test_fit_wants_the_model_among_its_replicas():
     a, b = co_net(9, 3), co_net(9, 3)
     with pytest.raises(ValueError, match="must contain"):
         fit(a, np.zeros((4, 9), np.float32), np.zeros((4, 3), np.float32), 1, replicas=[b], log=None)
+
+
+def test_param_total_of_the_listed_sizes():
+    """The library's parameter count against the state-dict shapes: the golden cases, the sizes DESIGN.md section 11 lists, and the
+    nets tests/test_gpu_mtfnn.py runs at tile heights 32 and 16."""
+    from diffsg_amd import _lib
+    from diffsg_amd.mtfnn import mlp_desc
+    L = _lib.lib()
+    nets = [(w, n, None) for w, n in MR.CASES.values()] + [
+        ((9, 32, 64, 16, 3), 3, 3523), ((128, 8, 16, 8, 128), 0, 2464), ((6, 64, 32, 16, 32, 5), 2, 3765),
+        ((64, 64, 32, 16, 32, 34), 2, 8434), ((128, 64, 64, 128), 64, 20736), ((128, 64, 64, 64, 64, 128), 0, 29056)]
+    for widths, n_sig, want in nets:
+        got = L.dsg_mlp_param_total(ctypes.byref(mlp_desc(widths, n_sig)))
+        assert got == sum(int(np.prod(s)) for _, s in MR.shapes(widths)) and (want is None or got == want), widths
+
+
+@pytest.mark.parametrize("what,widths,n_sig,n_layers", [
+    ("one layer", (9, 3), 3, 1),
+    ("six layers", (9, 32, 64, 16, 8, 3), 3, 6),
+    ("hidden width 65", (9, 32, 65, 16, 3), 3, 4),
+    ("input width 129", (129, 32, 64, 16, 3), 3, 4),
+    ("output width 129", (9, 32, 64, 16, 129), 3, 4),
+    ("n_sig above the output width", (9, 32, 64, 16, 3), 4, 4),
+])
+def test_descriptor_limits_are_refused(what, widths, n_sig, n_layers):
+    """Refused on the host, before any device call: runs without a GPU."""
+    from diffsg_amd import _lib
+    from diffsg_amd.mtfnn import mlp_desc
+    d = mlp_desc(widths, n_sig)
+    d.n_layers = n_layers
+    L = _lib.lib()
+    one = ctypes.c_void_p(16)           # never dereferenced: the descriptor is refused first
+    calls = {
+        "dsg_mlp_forward": lambda: L.dsg_mlp_forward(ctypes.byref(d), one, one, one, 8, None),
+        "dsg_mlp_loss_grad": lambda: L.dsg_mlp_loss_grad(ctypes.byref(d), one, one, one, 8, one, one, None),
+        "dsg_mlp_train_epoch": lambda: L.dsg_mlp_train_epoch(ctypes.byref(d), one, one, one, one, one, one, 8, 4, 0.005, 0.9, 0.999, 1e-8, 0,
+                                                             one, 1, None),
+    }
+    for name, call in calls.items():
+        assert call() != 0, (what, name)
+        msg = L.dsg_last_error().decode()
+        assert name in msg and len(msg) > len(name) + 4, msg
+    assert L.dsg_mlp_param_total(ctypes.byref(d)) == -1
+    assert "dsg_mlp_param_total" in L.dsg_last_error().decode()

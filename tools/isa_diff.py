@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""Are the baseline kernels of two source trees the same code?  usage: isa_diff.py OLD_TREE NEW_TREE [KERNEL-NAME REGEX]
+
+Compiles `#include "dsg_ppo.hpp"` (which includes dsg_mlp.hpp: the six k_mlp_* / k_ppo_* kernels) from each tree to gfx950 assembly
+with the flags of _lib.build(), no GPU needed, and prints per kernel `identical` assembly, or else whether the listing of its `_f32` /
+`_f64` opcodes agrees in program order with vector register numbers blanked, and the register, scratch and LDS
+figures of both.  Exit status 1 unless every kernel is at least `fp-order-same` with equal figures."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -mllvm -pragma-unroll-threshold=200000 -S --cuda-device-only".split()
+FIGURES = ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize")
+
+
+def kernels(tree, tmp):
+    """{kernel name: (instruction lines, {figure: value})} of the tree's baseline headers."""
+    src, asm = os.path.join(tmp, "tu.hip"), os.path.join(tmp, "tu.s")
+    with open(src, "w") as f:
+        f.write('#include <hip/hip_runtime.h>\n#include "dsg_ppo.hpp"\n')
+    inc = ["-I", os.path.join(tree, "diffsg_amd", "csrc"), "-I", os.path.join(tree, "include")]
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + inc + ["-o", asm, src], check=True)
+    with open(asm) as f:
+        txt = f.read()
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:.*?-- End function(.*?)(?=^\t\.text|\Z)", txt, re.M | re.S):
+        name = re.search(r"\d(k_[a-z0-9_]+)E", m.group(1))            # the kernels' names are lower case: the first E ends the name
+        body = [ln.split(";")[0].strip() for ln in m.group(2).split("\n")]
+        out[name.group(1) if name else m.group(1)] = ([ln for ln in body if ln],
+                                                      {k: int(re.search(rf"; {k}: (\d+)", m.group(3)).group(1)) for k in FIGURES})
+    return out
+
+
+def fp_listing(lines):
+    return [re.sub(r"\bv(\d+|\[\d+:\d+\])", "v", ln) for ln in lines if re.match(r"\w*_f(32|64)\b", ln)]
+
+
+def main(old_tree, new_tree, want="k_(mlp|ppo)_"):
+    with tempfile.TemporaryDirectory() as tmp:
+        old, new = kernels(old_tree, tmp), kernels(new_tree, tmp)
+    bad = sorted(k for k in set(old) ^ set(new) if re.search(want, k))
+    for k in sorted(k for k in set(old) & set(new) if re.search(want, k)):
+        (lo, fo), (ln, fn) = old[k], new[k]
+        a, b = fp_listing(lo), fp_listing(ln)
+        verdict = "identical" if lo == ln else "fp-order-same" if a == b else "fp-multiset-same" if sorted(a) == sorted(b) else "DIFFERENT"
+        if verdict not in ("identical", "fp-order-same") or fo != fn:
+            bad.append(k)
+        print(f"{k:16s} {verdict:16s} {len(lo)} / {len(ln)} lines, {len(a)} / {len(b)} fp   " + "  ".join(f"{f} {fo[f]} / {fn[f]}" for f in FIGURES))
+    if bad:
+        sys.exit("NOT the same: " + ", ".join(bad))
+
+
+if __name__ == "__main__":
+    main(*sys.argv[1:4])
