@@ -222,6 +222,12 @@ _SIGS = {
     "dsg_ppo_train_epoch": (ctypes.c_int, [ctypes.POINTER(PpoDesc)] + [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_void_p]),
+    "dsg_gd_co": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dsg_gd_msr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dsg_gd_nu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                 ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "dsg_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong,
                                   ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_void_p]),

@@ -17,6 +17,7 @@
 #include "dsg_nugen.hpp"
 #include "dsg_mlp.hpp"
 #include "dsg_ppo.hpp"
+#include "dsg_gd.hpp"
 #include "dsg_own.hpp"
 #include "../../include/diffsg.h"
 
@@ -3494,6 +3495,59 @@ int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg,
     if (!p.onchip) { HIPCK(gws.alloc((size_t)R * p.P, s)); e.gws = gws; }
     if (buf_off < 0) { HIPCK(bws.alloc((size_t)R * bufrows * (2 * p.A + 2), s)); e.bufws = bws; }
     return baseline_launch(k_ppo_epoch, R, bytes, s, {&gws, &bws}, p, e);
+}
+
+}  // extern "C"
+
+// ---- The gradient-descent baseline (dsg_gd.hpp): every iteration of a row in one launch.
+namespace {
+// What the three entry points check alike; D: state entries per row.
+int gd_args(const char* who, const double* X, const double* Y, long long B, int iters, const double* rec, int rec_every) {
+    if (B < 0 || B > 0x7fffffffLL) return fail("%s: B = %lld rows (0 .. 2^31 - 1)", who, B);
+    if (iters < 0) return fail("%s: iters = %d", who, iters);
+    if (rec_every < 0) return fail("%s: rec_every = %d", who, rec_every);
+    if (rec && rec_every == 0) return fail("%s: a record buffer needs rec_every > 0", who);
+    if (B > 0 && (!X || !Y)) return fail("%s: null argument", who);
+    return 0;
+}
+long long gd_grid(long long lanes) { return (lanes + kGdThreads - 1) / kGdThreads; }
+}  // namespace
+
+extern "C" {
+
+int dsg_gd_co(const double* X, double* Y, long long B, int n, int iters, double lr, double lambda1, double lambda2, double* rec,
+              int rec_every, void* stream) {
+    if (n < 1 || n > kGdCoMaxNodes) return fail("dsg_gd_co: n = %d nodes (1 .. %d)", n, kGdCoMaxNodes);
+    if (gd_args("dsg_gd_co", X, Y, B, iters, rec, rec_every)) return 1;
+    if (B == 0 || iters == 0) return 0;
+    const GdRec r{rec, rec_every};
+    hipStream_t s = (hipStream_t)stream;
+    if (n <= 4) return baseline_launch(k_gd_co<4>, gd_grid(B), 0, s, {}, X, Y, B, n, iters, lr, lambda1, lambda2, r);
+    if (n <= 8) return baseline_launch(k_gd_co<8>, gd_grid(B), 0, s, {}, X, Y, B, n, iters, lr, lambda1, lambda2, r);
+    return baseline_launch(k_gd_co<16>, gd_grid(B), 0, s, {}, X, Y, B, n, iters, lr, lambda1, lambda2, r);
+}
+
+int dsg_gd_msr(const double* X, double* Y, long long B, int M, int iters, double lr, double* rec, int rec_every, void* stream) {
+    if (M < 1 || M > kGdMsrMax) return fail("dsg_gd_msr: M = %d channels (1 .. %d)", M, kGdMsrMax);
+    if (gd_args("dsg_gd_msr", X, Y, B, iters, rec, rec_every)) return 1;
+    if (B == 0 || iters == 0) return 0;
+    const GdRec r{rec, rec_every};
+    hipStream_t s = (hipStream_t)stream;
+    if (M <= kGdMsrSlots) return baseline_launch(k_gd_msr<1>, gd_grid(B), 0, s, {}, X, Y, B, M, iters, lr, r);
+    return baseline_launch(k_gd_msr<kGdMsrLanes>, gd_grid(B * kGdMsrLanes), 0, s, {}, X, Y, B, M, iters, lr, r);
+}
+
+int dsg_gd_nu(const double* X, double* Y, long long B, int K, int iters, double lr, double p_ref, double* rec, int rec_every,
+              void* stream) {
+    if (K < 1 || K > kGdNuMaxUsers) return fail("dsg_gd_nu: K = %d users (1 .. %d)", K, kGdNuMaxUsers);
+    if (gd_args("dsg_gd_nu", X, Y, B, iters, rec, rec_every)) return 1;
+    if (B == 0 || iters == 0) return 0;
+    const GdRec r{rec, rec_every};
+    hipStream_t s = (hipStream_t)stream;
+    if (K <= 4) return baseline_launch(k_gd_nu<4>, gd_grid(B), 0, s, {}, X, Y, B, K, iters, lr, p_ref, r);
+    if (K <= 8) return baseline_launch(k_gd_nu<8>, gd_grid(B), 0, s, {}, X, Y, B, K, iters, lr, p_ref, r);
+    if (K <= 16) return baseline_launch(k_gd_nu<16>, gd_grid(B), 0, s, {}, X, Y, B, K, iters, lr, p_ref, r);
+    return baseline_launch(k_gd_nu<32>, gd_grid(B), 0, s, {}, X, Y, B, K, iters, lr, p_ref, r);
 }
 
 }  // extern "C"

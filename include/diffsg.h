@@ -352,6 +352,22 @@ int dsg_ppo_train_epoch(const dsg_ppo_desc* desc, float* params, float* exp_avg,
                         float* old_logp, const float* noise, const int* perm, int N, int batch, double lr, double beta1, double beta2,
                         double eps, long long step0, float* batch_out, int R, void* stream);
 
+/* ---- The gradient-descent baseline (baselines/GD.py), csrc/dsg_gd.hpp.  float64 throughout, like the reference's numpy.  One launch runs
+ * all `iters` iterations of every row in registers: Y [B][D] is the start state on entry and the final state on return (iters == 0
+ * leaves it untouched, B == 0 launches nothing).  With rec != NULL and rec_every > 0 the state after iterations rec_every,
+ * 2 * rec_every, ... is also stored to rec [iters / rec_every][B][D].  No contraction, the reference's operation order, IEEE division, no
+ * clamps: a zero allocation yields the inf / NaN numpy yields.  Calls compose exactly: a iterations followed by b iterations are
+ * bit-identical to a + b.  Stream-ordered.
+ *   dsg_gd_co  (GD.py:12-36):   X [B][3n], Y [B][2n] = decisions | allocations, Y -= grad * lr; 1 <= n <= 16.
+ *   dsg_gd_msr (GD.py:62-83):   X [B][M] gains, Y [B][M], Y += grad * lr; 1 <= M <= 128.  The row sum's order is the device's own.
+ *   dsg_gd_nu  (GD.py:100-117): X [B][2K] user coordinates as the loader scales them, Y [B][2 + K] = position | powers,
+ *                               Y += grad * lr; 1 <= K <= 32; p_ref: the centre of the power penalty (18 in the reference). */
+int dsg_gd_co(const double* X, double* Y, long long B, int n, int iters, double lr, double lambda1, double lambda2, double* rec,
+              int rec_every, void* stream);
+int dsg_gd_msr(const double* X, double* Y, long long B, int M, int iters, double lr, double* rec, int rec_every, void* stream);
+int dsg_gd_nu(const double* X, double* Y, long long B, int K, int iters, double lr, double p_ref, double* rec, int rec_every,
+              void* stream);
+
 /* Measurement hooks for bench.py: the per-step operator list and a timed replay of one operator's kernel with HIP
  * events on `stream` (rows = B rows, both passes, as inside dsg_sample). */
 int dsg_op_count(const dsg_handle* h);
