@@ -1733,7 +1733,11 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
         for (const ColsumDesc& c : cd) if (c.gmax_slot >= 0) seen[c.gmax_slot] = 1;
         for (int sl : bwd_slots) seen[sl] = 1;
         for (const WgradDesc& w : wd) if (!seen[w.gmax_slot]) { fail("internal: weight-gradient operand without a tracked maximum"); return 1; }
-        if ((int)gsrc.size() > kMaxGmax) { fail("internal: too many gradient tensors (%d)", (int)gsrc.size()); return 1; }
+        if ((int)gsrc.size() > kMaxGmax) {
+            fail("dsg_train_step: this net (n_res %d, n_blocks %d) has %d gradient tensors whose maximum is tracked (3 per residual block, "
+                 "1 per Linear); training supports at most %d", h->d.n_res, h->d.n_blocks, (int)gsrc.size(), kMaxGmax);
+            return 1;
+        }
         h->n_gmax = (int)gsrc.size();
     }
     // Launch order of the (descriptor, k-block, row-chunk) units:
@@ -1894,7 +1898,8 @@ static dsg_handle* create_impl(const dsg_unet_desc* desc, const int* is_attn, in
     if (d.n_res < 1 || d.n_res > 8 || d.n_blocks < 1 || d.input_dim < 1 || d.cond_dim < 1) {
         fail("bad UNet1D descriptor"); return nullptr;
     }
-    if (d.input_dim > 128 || d.cond_dim > 4096) { fail("input_dim > 128 is not supported"); return nullptr; }
+    if (d.input_dim > 128) { fail("input_dim %d is not supported (at most 128)", d.input_dim); return nullptr; }
+    if (d.cond_dim > 4096) { fail("cond_dim %d is not supported (at most 4096)", d.cond_dim); return nullptr; }
     if (!width_supported(d.proj_dim) || d.proj_dim < 8) {
         fail("proj_dim %d unsupported (supported block widths: 4 (dims only), 8, 16, 32, 64, 128)", d.proj_dim); return nullptr;
     }

@@ -101,6 +101,29 @@ def test_a_short_flag_list_with_a_flag_set_is_refused():
         UNet1D(input_dim=3, proj_dim=16, cond_dim=3, dims=(16, 8, 8, 8), is_attn=(True, False, False))
 
 
+@pytest.mark.parametrize("field,limit", [("input_dim", 128), ("cond_dim", 4096)])
+def test_each_size_limit_of_the_descriptor_is_refused_under_its_own_name(field, limit):
+    """dsg_create checks the descriptor before it looks for a device: input_dim > 128 and cond_dim > 4096 are refused, each with a message
+    that names the field, the value and the limit (cond_dim used to be reported as "input_dim > 128")."""
+    import ctypes
+    from diffsg_amd import _lib
+    L = _lib.lib()
+    d = _lib.UNetDesc()
+    d.input_dim, d.proj_dim, d.cond_dim, d.n_blocks, d.n_res = 3, 16, 3, 1, 1
+    d.dims[0] = 8
+    setattr(d, field, limit + 1)
+    assert not L.dsg_create(ctypes.byref(d))
+    msg = L.dsg_last_error().decode()
+    other = "cond_dim" if field == "input_dim" else "input_dim"
+    assert field in msg and str(limit + 1) in msg and str(limit) in msg and other not in msg, msg
+    setattr(d, field, limit)                     # the limit itself passes the descriptor checks (what stops it without a GPU is the device)
+    hd = L.dsg_create(ctypes.byref(d))
+    if hd:
+        L.dsg_destroy(hd)
+    else:
+        assert "no HIP device" in L.dsg_last_error().decode()
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_cpu_restatement_is_the_reference(gold, name):
     """attn_ref (the oracle's pieces + the two-GEMM closed form) IS the reference at the golden's shape, max|diff| = 0, for the forward,
