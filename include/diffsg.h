@@ -7,7 +7,16 @@
  *   - all pointers are DEVICE pointers to float32 (row-major, contiguous) unless stated; the library borrows them for
  *     the duration of the call and owns only its packed-weight arena and workspace (allocated in dsg_create /
  *     dsg_reserve / lazily on the first call of a new batch size, never while a graph is being captured);
- *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, the calls do not synchronise;
+ *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it (any stream, also a non-blocking one: work the library puts
+ *     on streams of its own forks from `stream` and joins back into it inside the call), and a call that repeats the previous call's
+ *     shapes, pointers and settings does not synchronise.  A call synchronises `stream` (or the device) where it has to rebuild something:
+ *     workspace growth, the first dsg_bind_weights or one with other pointers, another batch size, precision mode, option or launch
+ *     policy, and dsg_unet_forward with another x / out pointer than its previous call (its launch tables hold them).  By design every
+ *     call synchronises `stream` in: dsg_sample* under DSG_PRECISION_F32_MFMA on a net with blocks of at most 32 features (a table
+ *     upload from a reused host buffer), dsg_sample_chunked (the per-chunk seeds come from pageable host memory), DSG_SAMPLE_PROFILE,
+ *     dsg_range_status*, dsg_time_op and dsg_box_calibrate (tests/test_gpu_streams.py pins both lists);
+ *   - one handle may be used from several streams, one call at a time: the caller orders the streams (the second one waits for an event
+ *     of the first), the library adds no ordering of its own between calls;
  *   - int functions return 0 on success, non-zero on error; dsg_last_error() gives the message (thread local);
  *   - a handle is bound to the device that was current in dsg_create and is used by one host thread at a time.
  */
