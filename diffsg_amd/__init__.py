@@ -9,8 +9,9 @@ from .ema import ExponentialMovingAverage  # noqa: F401
 from .repeated import BestOf, best_of  # noqa: F401
 from .mtfnn import MTFNN, co_net, msr_net  # noqa: F401
 from .ppo import PPOAgent  # noqa: F401
+from .steps import StepPlan, strided, ddim, tail  # noqa: F401
 from .gd import co_descent, msr_descent, nu_descent, gd_co, gd_msr, gd_nu  # noqa: F401
 
 __all__ = ["UNet1D", "generate_cosine_schedule", "init_weights", "ExponentialMovingAverage", "BestOf", "best_of", "MTFNN", "co_net", "msr_net",
-           "PPOAgent", "co_descent", "msr_descent", "nu_descent", "gd_co", "gd_msr",
+           "PPOAgent", "StepPlan", "strided", "ddim", "tail", "co_descent", "msr_descent", "nu_descent", "gd_co", "gd_msr",
            "gd_nu"]

@@ -124,28 +124,32 @@ def customized_real_decoder(Y_pred):
 
 
 @torch.no_grad()
-def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print, repeats=1):
+def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print, repeats=1, steps=None,
+                 sampler="strided", eta=0.0):
     """classifier_free_CO.py:293-356.  `repeats` > 1: that many draws per test row, the one with the lowest cost scored
-    (DDPM.sample_best); 1 is the reference's single draw."""
+    (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     device = _device()
     diffusion_model = build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config)
     diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
     diffusion_model.to(device)
+    from .steps import make as make_plan
+    plan = make_plan(diffusion_model, steps, sampler, eta)
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
     if repeats > 1:
-        best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size)
+        best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan)
         Yd, pred_cost = best.solution, best.objective
     else:
         # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
         # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
         if batch_size % 32 == 0:
-            Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
+            Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
         else:
-            Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
+            Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
         Yd = customized_real_decoder(Y_pred)
         pred_cost = cost_calc(Xt, Yd)
     true_cost = cost_calc(Xt, Yt)

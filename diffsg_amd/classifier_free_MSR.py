@@ -98,21 +98,26 @@ def custom_decoder(Y_pred):
 
 
 @torch.no_grad()
-def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print, repeats=1):
+def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print, repeats=1, steps=None,
+                  sampler="strided", eta=0.0):
     """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats` > 1: that many draws per test
-    row, the one with the best sum rate scored (DDPM.sample_best); 1 is the reference's single draw."""
+    row, the one with the best sum rate scored (DDPM.sample_best); 1 is the reference's single draw.
+    `steps` = K: sample on K of the T trained steps
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
     _, _, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
     diffusion_model = build_model(M, custom_config['sfn'] * M, device, T, custom_config, W)
     diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
     diffusion_model.to(device)
+    from .steps import make as make_plan
+    plan = make_plan(diffusion_model, steps, sampler, eta)
     X = torch.tensor(X_test, dtype=torch.float32)
     if repeats > 1:
         Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
         Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
         from .decode import msr_rate
-        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size).objective
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan).objective
         true_rate = msr_rate(Yt, Xt)
         out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
                "avg_rate_diff": float(torch.mean(pred_rate - true_rate)), "repeats": int(repeats)}
@@ -123,9 +128,9 @@ def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batc
     # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
     # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
     if batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
+        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
     else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
+        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
     from .decode import msr_rate

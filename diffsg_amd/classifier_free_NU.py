@@ -107,24 +107,27 @@ def rate_calc(Y_pred_decoded, X):
 
 @torch.no_grad()
 def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, width=400, height=400,
-                 log=print, repeats=1):
+                 log=print, repeats=1, steps=None, sampler="strided", eta=0.0):
     """classifier_free_NU.py:306-361.  `repeats` > 1: that many draws per test row, the one with the best rate scored
-    (DDPM.sample_best); 1 is the reference's single draw."""
+    (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
     _, _, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
     device = _device()
     diffusion_model = build_model(K, P_sum, device, T, custom_config)
     diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
     diffusion_model.to(device)
+    from .steps import make as make_plan
+    plan = make_plan(diffusion_model, steps, sampler, eta)
     X = torch.tensor(X_test, dtype=torch.float32)
     # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
     # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
     if repeats > 1:
         Y_pred = None                       # sampled below, `repeats` rounds of the same calls
     elif batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
+        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
     else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
+        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
     Xt = X.to(device).clone()
     Xt[:, 0::2] *= width
     Xt[:, 1::2] *= height
@@ -134,7 +137,7 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
     Yt[:, 2:] *= P_sum
     if repeats > 1:
         # width / height of THIS call, as custom_decoder below gets them (the hook reads the model's custom_config: the same values)
-        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size).objective
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan).objective
     else:
         pred_rate = rate_calc(custom_decoder(Y_pred, width, height, P_sum), Xt)
     true_rate = rate_calc(Yt, Xt)

@@ -211,6 +211,9 @@ struct dsg_handle {
     DevBuf<float> freq;         // [proj/2]
     DevBuf<double> red;         // [2][kRedBlocks]
     DevBuf<int> step_dev;
+    // dsg_set_step_grid: the time value of every step index of a sampling call and the number of early renormalised steps; grid_n == 0: no
+    // grid (t = i / T, min(T, 4) renorm steps).  The buffer only grows and is kept when the grid is removed.
+    DevBuf<float> grid_dev; int grid_n = 0, grid_cap = 0, grid_renorm = 0;
     double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device, not owned), reduced across ranks by `renorm_fn`
     void (*renorm_fn)(void*) = nullptr; void* renorm_user = nullptr;
     int device = 0;              // the device that was current in dsg_create: the settings / status entry points select it themselves
@@ -482,6 +485,10 @@ __global__ void k_iota(int* p, int n) {
 }
 __global__ void k_linspace_t(float* p, int T) {  // t = i / T in float32, as `torch.full(..., i) / T` (MSR.py:126)
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < T; i += gridDim.x * blockDim.x) p[i] = (float)i / (float)T;
+}
+
+__global__ void k_grid_t(float* p, const float* __restrict__ grid, int n) {  // dsg_set_step_grid: the handle's own time values
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = grid[i];
 }
 
 int ensure_workspace(dsg_handle* h, int rows, int entries) {
@@ -2349,6 +2356,25 @@ int dsg_set_renorm_hook(dsg_handle* h, double* stats3, void (*reduce)(void*), vo
     return 0;
 }
 
+int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_steps) {
+    if (!h) return fail("null handle");
+    if (n < 0) return fail("dsg_set_step_grid: n = %d is negative", n);
+    if (!t_host || n == 0) { h->grid_n = 0; return 0; }     // nothing is overwritten: an enqueued call keeps reading the buffer
+    if (renorm_steps < -1 || renorm_steps > n) return fail("dsg_set_step_grid: renorm_steps = %d is outside -1 .. n = %d", renorm_steps, n);
+    DeviceGuard dg(h);
+    // an enqueued call may still copy the old grid; the step graphs do not depend on it and stay
+    HIPCK(hipDeviceSynchronize());
+    if (n > h->grid_cap) {
+        h->grid_n = 0; h->grid_cap = 0;
+        HIPCK(h->grid_dev.alloc((size_t)n));
+        h->grid_cap = n;
+    }
+    HIPCK(hipMemcpy(h->grid_dev, t_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    h->grid_n = n;
+    h->grid_renorm = renorm_steps < 0 ? (n < 4 ? n : 4) : renorm_steps;
+    return 0;
+}
+
 int dsg_set_option(dsg_handle* h, int option, int value) {
     if (!h) return fail("null handle");
     DeviceGuard dg(h);
@@ -2508,6 +2534,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     if (check_bound(h)) return 1;
     if (B < 1 || T < 1) return fail("B and T must be >= 1");
     if (!coef || !cond || !out) return fail("dsg_sample: null pointer argument");
+    if (h->grid_n && T != h->grid_n) return fail("dsg_sample: the handle's step grid (dsg_set_step_grid) has %d steps, the call has T = %d", h->grid_n, T);
     const int chunks = chunk_rows > 0 ? cdiv(B, chunk_rows) : 1;
     if (chunk_rows > 0 && (chunk_rows % 32 != 0)) return fail("dsg_sample_chunked: chunk_rows must be a multiple of 32 (a row tile)");
     if (chunks > 1 && h->renorm_fn) return fail("dsg_sample_chunked: a renorm hook (sharded global renorm) and chunking exclude each other");
@@ -2535,7 +2562,8 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     }
 
     // per-call setup: time table for all T steps, condition fragments, start state, step counter
-    hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->fw.tvals, T);
+    if (h->grid_n) hipLaunchKernelGGL(k_grid_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->fw.tvals, (const float*)h->grid_dev, T);
+    else hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->fw.tvals, T);
     run_time_path(h, T, s);
     hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tpp * CG * 256, 256)), dim3(256), 0, s, cond, (const float*)nullptr, B,
                        h->d.cond_dim, CG, h->fw.condfrag, tpp);
@@ -2556,7 +2584,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
-    const int n_renorm = T < 4 ? T : 4;  // steps i > T-5 (MSR.py:136)
+    const int n_renorm = h->grid_n ? h->grid_renorm : (T < 4 ? T : 4);  // steps i > T-5 (MSR.py:136), or dsg_set_step_grid's count
     if (flags & DSG_SAMPLE_PROFILE) {
         const size_t nops = h->ops.size();
         h->op_ms.assign(nops, 0.0);

@@ -75,7 +75,7 @@ class DDPMCore(nn.Module):
 
     @torch.no_grad()
     def sample(self, cond, omega=1.0, *, y_T=None, noise=None, seed=None, host_rng=False, use_graph=True,
-               profile=False, check_range=True):
+               profile=False, check_range=True, plan=None):
         """Guided reverse sampling; returns y_0 of shape (B, D).
 
         Beyond the reference's `(cond, omega)`:
@@ -90,7 +90,10 @@ class DDPMCore(nn.Module):
                       kernels with the same draws, then restores the caller's precision mode.  `check_range=False` only
                       enqueues (consecutive calls pipeline); the flag is then sticky: the NEXT sample / sample_chunked /
                       forward on this object raises if that call's results were saturated.
+          plan        a `steps.StepPlan`: run its K steps (a sub-sequence of the trained ones, or the last k + 1) instead of all T;
+                      `noise` is then (K-2, B, D) and the recorded trajectory (B, K*D).  None: all T trained steps.
         """
+        K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
             raise RuntimeError("DDPM.sample: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
         self._raise_if_unchecked_call_saturated()
@@ -100,10 +103,10 @@ class DDPMCore(nn.Module):
             # draw once here so that a repeat uses the same start state and noise
             B0, D0 = cond.shape[0], self.model.cfg["input_dim"]
             y_T = torch.randn(B0, *self.data_size).reshape(B0, D0)
-            zs = [torch.randn(B0, *self.data_size).reshape(B0, D0) for i in range(self.T - 1, 1, -1)]
+            zs = [torch.randn(B0, *self.data_size).reshape(B0, D0) for i in range(K - 1, 1, -1)]
             noise = torch.stack(zs) if zs else torch.zeros(0, B0, D0)
             host_rng = False
-        out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile)
+        out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan)
         if cond.shape[0] == 0:
             return out
         if not check_range:
@@ -116,7 +119,7 @@ class DDPMCore(nn.Module):
             prev = self.model.precision
             self.model.set_precision("f32")
             try:
-                out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile)
+                out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan)
             finally:
                 self.model.set_precision(prev)
         return out
@@ -131,9 +134,55 @@ class DDPMCore(nn.Module):
                                    "split-f16 path (|x| > 6e4): its results are invalid -- repeat it with check_range=True or "
                                    "model.set_precision('f32')")
 
-    def _sample_once(self, cond, omega, y_T, noise, seed, host_rng, use_graph, profile):
+    def _plan_steps(self, plan, cond, noise):
+        """Number of steps of a call, after the checks of a plan that need no device: its shape, the noise-free last two steps (with
+        injected noise the update reads row K-1-i of a (K-2)-row tensor at step i) and the shape of the injected noise."""
+        if plan is None:
+            return self.T
+        K = len(plan.taus)
+        if K < 1 or tuple(plan.t.shape) != (K,) or tuple(plan.coef.shape) != (K, 4):
+            raise ValueError(f"step plan: {K} taus need t of shape ({K},) and coef of shape ({K}, 4)")
+        if not 0 <= int(plan.renorm_steps) <= K:
+            raise ValueError(f"step plan: renorm_steps = {plan.renorm_steps} is outside 0 .. {K}")
+        if bool((plan.coef[:2, 3] != 0).any()):
+            raise ValueError("step plan: steps 0 and 1 must be noise free (coef[:2, 3] == 0): the noise tensor has K - 2 rows")
+        if noise is not None:
+            want = (max(K - 2, 0), cond.shape[0], self.model.cfg["input_dim"])
+            if tuple(noise.shape) != want:
+                raise ValueError(f"noise must have shape {want} for a plan of {K} steps")
+        return K
+
+    def _use_plan(self, hd, plan, dev):
+        """Make handle `hd` hold `plan`'s step grid (none for plan=None) and return the plan's coefficient table on `dev`.  What the
+        handle holds is remembered beside it, so that repeated calls with one plan set nothing: setting a grid synchronises the device."""
+        import ctypes
+        nat = self.model._native
+        held = getattr(nat, "step_grid", None)          # (handle, plan, coef on the device)
+        if held is not None and held[0] != hd:
+            held = None
+        if plan is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_step_grid(hd, None, 0, -1))
+                nat.step_grid = None
+            return self._coef_table()
+        coef = plan.coef
+        if held is not None and held[1].coef is coef and held[2].device == dev:
+            coef = held[2]
+        else:
+            coef = coef.detach().to(dev, torch.float32).contiguous()    # the trained table's own rows are already there
+        same = held is not None and (held[1] is plan or (int(held[1].renorm_steps) == int(plan.renorm_steps)
+                                                          and torch.equal(held[1].t, plan.t)))
+        if not same:
+            t = plan.t.detach().cpu().to(torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().dsg_set_step_grid(hd, ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float)), t.numel(),
+                                                        int(plan.renorm_steps)))
+        nat.step_grid = (hd, plan, coef)
+        return coef
+
+    def _sample_once(self, cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan=None):
         hd = self.model.native_handle()
-        B, D, T = cond.shape[0], self.model.cfg["input_dim"], self.T
+        B, D, T = cond.shape[0], self.model.cfg["input_dim"], (self.T if plan is None else len(plan.taus))
         cond = cond.detach().to(torch.float32).contiguous()
         dev = cond.device
         if host_rng and y_T is None:
@@ -148,11 +197,11 @@ class DDPMCore(nn.Module):
                 raise ValueError(f"noise must have shape ({max(T - 2, 0)}, {B}, {D})")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        coef = self._coef_table()
         out = torch.empty(B, D, device=dev, dtype=torch.float32)
         rec = torch.empty(2, T, B, D, device=dev, dtype=torch.float32) if self.record_denoise_path else None
         if B == 0:
             return out                     # no rows, nothing to launch (the reference's loop runs on empty tensors)
+        coef = self._use_plan(hd, plan, dev)
         flags = 2 if profile else (0 if use_graph else 1)
         # T <= 2 has no noisy step (MSR.py:129): a null pointer (= device Philox) is then never dereferenced
         zptr = _lib.ptr(noise) if (noise is not None and noise.numel()) else _lib.ptr(None)
@@ -172,21 +221,24 @@ class DDPMCore(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample_chunked(self, cond, omega=1.0, chunk_rows=512, *, seeds=None, y_T=None, noise=None, use_graph=True, check_range=True):
+    def sample_chunked(self, cond, omega=1.0, chunk_rows=512, *, seeds=None, y_T=None, noise=None, use_graph=True, check_range=True,
+                       plan=None):
         """The reference's evaluation shape in one set of launches: `cond` is sampled as consecutive `chunk_rows`-row slices, each
         an independent `sample()` call (own start state and noise, own early-step renorm statistics; classifier_free_MSR.py:257,
         273-279).  Row for row bit-identical to `torch.cat([self.sample(cond[i:i + chunk_rows], omega, seed=seeds[k]) ...])`,
-        `seeds` = one Philox seed per chunk (default: drawn from torch's global generator, one per chunk, in chunk order)."""
+        `seeds` = one Philox seed per chunk (default: drawn from torch's global generator, one per chunk, in chunk order).
+        `plan`: as in `sample`, the same plan for every chunk."""
         import ctypes
+        K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
             raise RuntimeError("DDPM.sample_chunked: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
-        B, D, T = cond.shape[0], self.model.cfg["input_dim"], self.T
+        B, D, T = cond.shape[0], self.model.cfg["input_dim"], K
         if chunk_rows % 32 != 0:
             raise ValueError("chunk_rows must be a multiple of 32")
         nch = (B + chunk_rows - 1) // chunk_rows
         if nch <= 1:
             return self.sample(cond, omega, y_T=y_T, noise=noise, seed=None if seeds is None else int(seeds[0]), use_graph=use_graph,
-                               check_range=check_range)
+                               check_range=check_range, plan=plan)
         if self.record_denoise_path:
             # the trajectory ring belongs to one call (dsg_sample_rec): the chunked launch set has none
             raise RuntimeError("DDPM.sample_chunked does not record the de-noising trajectory: call sample() per chunk "
@@ -207,12 +259,15 @@ class DDPMCore(nn.Module):
                 raise ValueError(f"noise must have shape ({max(T - 2, 0)}, {B}, {D})")
         sd = (ctypes.c_ulonglong * nch)(*[int(x) & (2 ** 64 - 1) for x in seeds])
         zptr = _lib.ptr(noise) if (noise is not None and noise.numel()) else _lib.ptr(None)
-        coef = self._coef_table()
+        coef = None
 
         def launch():
+            nonlocal coef
             o = torch.empty(B, D, device=dev, dtype=torch.float32)
+            hd = self.model.native_handle()
+            coef = self._use_plan(hd, plan, dev)
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().dsg_sample_chunked(self.model.native_handle(), _lib.ptr(cond), _lib.ptr(y_T), zptr, sd, int(chunk_rows),
+                _lib.check(_lib.lib().dsg_sample_chunked(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, sd, int(chunk_rows),
                                                          float(omega), _lib.ptr(coef), T, _lib.ptr(o), B, 0 if use_graph else 1,
                                                          _lib.stream_ptr()))
             return o
@@ -255,7 +310,7 @@ class DDPMCore(nn.Module):
 
     @torch.no_grad()
     def sample_best(self, cond, X, n, omega=1.0, *, seeds=None, chunk_rows=None, max_rows=65536, use_graph=True, check_range=True,
-                    return_objectives=False):
+                    return_objectives=False, plan=None):
         """Repeated sampling: `n` rounds of `sample(cond, omega)` (of `sample_chunked(cond, omega, chunk_rows)` when `chunk_rows`
         is given), each decoded and scored against the unscaled features `X`, the best round kept per condition
         (`repeated.best_of`; returns its `BestOf`).
@@ -283,7 +338,7 @@ class DDPMCore(nn.Module):
             raise ValueError(f"sample_best: {n} rounds of {per_round} call(s) need {n * per_round} seeds, got {len(seeds)}")
         grouped = B > 0 and u % 32 == 0 and B % u == 0
         group = max(1, int(max_rows) // B) if grouped else 1
-        kw = dict(use_graph=use_graph, check_range=check_range)
+        kw = dict(use_graph=use_graph, check_range=check_range, plan=plan)   # every round runs the same step plan (None: all T steps)
         running = None
         for r0 in range(0, n, group):
             g = min(group, n - r0)
@@ -298,6 +353,21 @@ class DDPMCore(nn.Module):
                 Y = torch.cat([self.sample(cond[i * u:(i + 1) * u], omega, seed=sd[i], **kw) for i in range(per_round)])[None]
             running = best_of(problem, Y, X, out=running, round0=r0, return_objectives=return_objectives, **params)
         return running
+
+    @torch.no_grad()
+    def refine(self, cond, y_start, k, omega=1.0, *, q_noise=None, noise=None, seed=None, **kw):
+        """Noise a given solution `y_start` (B, D) to trained step `k` as q_sample does (MSR.py:103-104: float32 tensor operations on the
+        registered buffers; `q_noise` drawn with torch if not given) and run the reverse steps k .. 0 from there (`steps.tail`: the trained
+        table's own rows, no early renorm).  `noise` is (k-1, B, D); further keywords go to `sample`."""
+        from .steps import tail
+        plan = tail(self, k)
+        if not cond.is_cuda:
+            raise RuntimeError("DDPM.refine: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
+        dev = cond.device
+        y = y_start.detach().to(dev, torch.float32).reshape(cond.shape[0], -1)
+        q = torch.randn_like(y) if q_noise is None else q_noise.detach().to(dev, torch.float32).reshape(y.shape)
+        y_k = self.sqrt_alphas_cumprod[int(k)] * y + self.sqrt_one_minus_alphas_cumprod[int(k)] * q
+        return self.sample(cond, omega, plan=plan, y_T=y_k, noise=noise, seed=seed, **kw)
 
     def op_profile(self):
         """[(name, algorithmic flops/row/step, algorithmic bytes/row/step, ms_total, launches)] of the last

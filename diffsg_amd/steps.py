@@ -1,0 +1,129 @@
+"""Step plans: sampling on a sub-sequence of the trained timesteps.
+
+A `StepPlan` is what a `DDPM.sample(..., plan=...)` call needs beyond the model: which trained timestep every step index stands for
+(`taus`), the time value the denoiser sees there (`t`), the four scalars of the library's update per step (`coef`)
+
+    y <- (y - c1 * eps) * c2 + c3 * z,        z used iff c4 != 0
+
+and how many of the first steps of a call standardise y (`renorm_steps`; classifier_free_MSR.py:136-137).  Step index K-1 runs first,
+0 last.  Three constructors:
+
+  strided(ddpm, K)     K < T steps of the reference's own (ancestral) update rule, re-derived for the sub-sequence;
+  ddim(ddpm, K, eta)   DDIM (Song et al. 2021, eq. 12) on the same grid; deterministic at eta = 0;
+  tail(ddpm, k)        the last k + 1 trained steps with the trained table's own rows: refines a given state (DDPM.refine).
+
+Every table is computed on the host in float64 from the registered float32 `alphas_cumprod` buffer and cast to float32 once -- except
+where a plan IS the trained schedule (`strided(ddpm, T)`, `tail`): those reuse the rows of `ddpm._coef_table()` bit for bit, because that
+table is evaluated with float32 tensor operations and a float64 recomputation moves y_0 (8e-3 relative on the NU checkpoint at
+omega = 500).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+
+@dataclass(frozen=True, eq=False)
+class StepPlan:
+    taus: tuple                 # ints, strictly increasing: taus[j] is the trained timestep of step index j
+    t: torch.Tensor             # float32 [K]: taus / T, as the reference divides an int64 tensor (MSR.py:126)
+    coef: torch.Tensor          # float32 [K, 4]
+    renorm_steps: int           # the first `renorm_steps` steps of a call standardise y
+
+    @property
+    def K(self):
+        return len(self.taus)
+
+
+def _acp(ddpm):
+    return ddpm.alphas_cumprod.detach().cpu().double().numpy()
+
+
+def _grid(T, K, taus):
+    if taus is None:
+        K = int(K)
+        if not 2 <= K <= T:
+            raise ValueError(f"a step plan needs 2 <= K <= T = {T} steps, got K = {K}")
+        return tuple((j * (T - 1) + (K - 1) // 2) // (K - 1) for j in range(K))
+    tt = tuple(int(v) for v in taus)
+    if any(int(v) != v for v in taus):
+        raise ValueError("taus must be integers")
+    if K is not None and len(tt) != int(K):
+        raise ValueError(f"K = {K} but {len(tt)} taus given")
+    if not tt or tt[0] < 0 or tt[-1] > T - 1 or any(b <= a for a, b in zip(tt, tt[1:])):
+        raise ValueError(f"taus must be strictly increasing integers in [0, {T - 1}]")
+    return tt
+
+
+def _times(taus, T):
+    return torch.tensor(taus, dtype=torch.int64) / T
+
+
+def _is_identity(taus, T):
+    return len(taus) == T and taus[0] == 0 and taus[-1] == T - 1
+
+
+def strided(ddpm, K=None, taus=None):
+    """Ancestral sampling on `K` of the `T` trained steps: the reference's update (MSR.py:133-134) with the per-step alpha
+    replaced by a_j = acp[tau_j] / acp[tau_{j-1}] (a_0 = acp[tau_0]).  Default grid: K points from 0 to T-1, evenly spaced and
+    rounded to the nearest step.  `taus == range(T)` gives the trained schedule itself, its table reused bit for bit."""
+    T = ddpm.T
+    taus = _grid(T, K, taus)
+    if _is_identity(taus, T):
+        return StepPlan(taus, _times(taus, T), ddpm._coef_table(), min(T, 4))
+    acp = _acp(ddpm)
+    n = len(taus)
+    c = np.zeros((n, 4))
+    for j, tau in enumerate(taus):
+        at = acp[tau]
+        ap = acp[taus[max(j - 1, 0)]]
+        a = at / ap if j > 0 else at
+        c[j] = ((1.0 - a) / np.sqrt(1.0 - at), 1.0 / np.sqrt(a), (1.0 - ap) / (1.0 - at), float(j > 1))
+    return StepPlan(taus, _times(taus, T), torch.tensor(c, dtype=torch.float32), min(n, 4))
+
+
+def ddim(ddpm, K=None, eta=0.0, taus=None):
+    """DDIM(eta) on the grid of `strided`: with p the previous grid point (acp_p = 1 below step 0)
+    sigma = eta sqrt((1 - acp_p) / (1 - acp_t)) sqrt(1 - acp_t / acp_p);  y <- sqrt(acp_p / acp_t) (y - sqrt(1 - acp_t) eps)
+    + sqrt(1 - acp_p - sigma^2) eps + sigma z.  The last two steps are noise free for every eta (the noise tensor has K - 2 rows)."""
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    T = ddpm.T
+    taus = _grid(T, K, taus)
+    acp = _acp(ddpm)
+    n = len(taus)
+    c = np.zeros((n, 4))
+    for j, tau in enumerate(taus):
+        at = acp[tau]
+        ap = acp[taus[j - 1]] if j > 0 else 1.0
+        sig = eta * np.sqrt((1.0 - ap) / (1.0 - at)) * np.sqrt(max(1.0 - at / ap, 0.0))
+        c2 = np.sqrt(ap / at)
+        c[j] = (np.sqrt(1.0 - at) - np.sqrt(max(1.0 - ap - sig * sig, 0.0)) / c2, c2, sig, float(j > 1 and eta > 0.0))
+    return StepPlan(taus, _times(taus, T), torch.tensor(c, dtype=torch.float32), min(n, 4))
+
+
+def tail(ddpm, k, renorm_steps=0):
+    """The trained steps k .. 0 with the trained table's own rows: a partial run from a state at step k (DDPM.refine).  No early
+    renorm by default: the start state is a noised solution, not N(0, 1) noise."""
+    T = ddpm.T
+    if int(k) != k or not 0 <= int(k) <= T - 1:
+        raise ValueError(f"tail: k must be an integer in [0, {T - 1}], got {k}")
+    k = int(k)
+    if int(renorm_steps) != renorm_steps or not 0 <= int(renorm_steps) <= k + 1:
+        raise ValueError(f"tail: renorm_steps must be in [0, {k + 1}], got {renorm_steps}")
+    taus = tuple(range(k + 1))
+    return StepPlan(taus, _times(taus, T), ddpm._coef_table()[:k + 1], int(renorm_steps))
+
+
+def make(ddpm, steps=None, sampler="strided", eta=0.0):
+    """The plan of the entry points' `steps=, sampler=, eta=` keywords; None for `steps=None` (all T trained steps, no plan)."""
+    if steps is None:
+        return None
+    if sampler == "strided":
+        return strided(ddpm, steps)
+    if sampler == "ddim":
+        return ddim(ddpm, steps, eta)
+    raise ValueError(f"unknown sampler {sampler!r}: 'strided' or 'ddim'")

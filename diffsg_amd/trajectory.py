@@ -23,18 +23,22 @@ def _load(diffusion_model, ckpt_path, device):
 
 
 @torch.no_grad()
-def record_trajectories(diffusion_model, X_test, omega, batch_size=None):
+def record_trajectories(diffusion_model, X_test, omega, batch_size=None, steps=None, sampler="strided", eta=0.0):
     """(rows, T*D) float array of decoded trajectories.  batch_size=None: one `sample()` call over all rows (the MSR / NU
-    scripts); an int: chunks of that many rows written into place (co_trajectory_gen.py:48-56)."""
+    scripts); an int: chunks of that many rows written into place (co_trajectory_gen.py:48-56).  `steps` = K: the K-step
+    trajectory of `steps.strided` (`sampler="ddim"`: `steps.ddim` with `eta`), (rows, K*D); None: all T trained steps."""
+    from .steps import make as make_plan
+    plan = make_plan(diffusion_model, steps, sampler, eta)
+    K = diffusion_model.T if plan is None else plan.K
     dev = next(diffusion_model.model.parameters()).device
     X = torch.as_tensor(np.asarray(X_test), dtype=torch.float32)
     if batch_size is None:
-        diffusion_model.sample_checked(X.to(dev), omega)
+        diffusion_model.sample_checked(X.to(dev), omega, plan=plan)
         return np.asarray(diffusion_model.y_i_record)
     D = diffusion_model.model.cfg["input_dim"]
-    out = np.zeros((X.shape[0], D * diffusion_model.T), dtype=float)
+    out = np.zeros((X.shape[0], D * K), dtype=float)
     for i in range(0, X.shape[0], batch_size):
-        diffusion_model.sample_checked(X[i:i + batch_size].to(dev), omega)
+        diffusion_model.sample_checked(X[i:i + batch_size].to(dev), omega, plan=plan)
         out[i:i + batch_size, :] = diffusion_model.y_i_record
     return out
 

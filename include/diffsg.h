@@ -170,6 +170,22 @@ int dsg_sample_rec(dsg_handle* h, const float* cond, const float* y_T, const flo
 int dsg_sample_chunked(dsg_handle* h, const float* cond, const float* y_T, const float* noise, const unsigned long long* seeds,
                        int chunk_rows, float omega, const float* coef, int T, float* out, int B, int flags, void* stream);
 
+/* Sampling on a step grid of the caller's: a sub-sequence of the trained timesteps (strided ancestral sampling, DDIM) or the last
+ * k + 1 of them (a partial run from a given state).  dsg_sample, dsg_sample_rec and dsg_sample_chunked already take the per-step
+ * coefficients from the caller; this per-handle setting supplies the other two things a call derives from T:
+ *   t_host        HOST array of n floats: t_host[i] is the time value the denoiser sees at step index i (a call runs i = n-1 first, 0
+ *                 last), already divided, as the `t` of dsg_unet_forward;
+ *   renorm_steps  how many of the FIRST steps of a call standardise y (classifier_free_MSR.py:136-137): 0 .. n, or -1 for min(n, 4).
+ * t_host == NULL or n == 0 removes the grid: t = i / T and min(T, 4) renorm steps, as without this call.
+ * While a grid is set, a sampling call whose T differs from n fails before anything is enqueued; `coef` is [n][4], `noise` [n-2][B][D],
+ * the records [n][B][D], and with a renorm hook installed the hook is called on exactly the renorm_steps first steps.  Steps 0 and 1
+ * MUST carry a zero noise flag (coef[i][3] == 0 for i < 2): with caller-supplied noise step i reads row n-1-i of an [n-2]-row tensor,
+ * and the library cannot see `coef` on the host.  dsg_unet_forward and the training steps ignore the grid.
+ * The grid is copied into a device buffer the handle owns.  Like the other settings calls this one takes no stream: it selects the
+ * handle's device itself and synchronises that device before it overwrites the buffer (an enqueued call may still read it); removing
+ * the grid does not synchronise.  The captured step graphs do not depend on the grid and are kept. */
+int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_steps);
+
 /* One training step's forward + backward: loss = DDPM.forward(y, cond) (classifier_free_MSR.py:100-112) and
  * d(loss)/d(theta) for every denoiser tensor, as `loss.backward()` produces them (classifier_free_MSR.py:223-224).
  *   y [B][D], cond [B][C] row-major;  ts [B] int32 in [0,T);  noise [B][D];  cond_mask [B] (0/1) -- the three random
