@@ -125,10 +125,12 @@ def customized_real_decoder(Y_pred):
 
 @torch.no_grad()
 def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print, repeats=1, steps=None,
-                 sampler="strided", eta=0.0):
+                 sampler="strided", eta=0.0, variants=None):
     """classifier_free_CO.py:293-356.  `repeats` > 1: that many draws per test row, the one with the lowest cost scored
     (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
+    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
+    single-setting spelling and are not read then."""
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     device = _device()
@@ -137,11 +139,13 @@ def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, bat
     diffusion_model.to(device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
+    if variants is not None and repeats < 2:
+        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
     if repeats > 1:
-        best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan)
+        best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants)
         Yd, pred_cost = best.solution, best.objective
     else:
         # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as

@@ -99,11 +99,13 @@ def custom_decoder(Y_pred):
 
 @torch.no_grad()
 def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print, repeats=1, steps=None,
-                  sampler="strided", eta=0.0):
+                  sampler="strided", eta=0.0, variants=None):
     """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats` > 1: that many draws per test
     row, the one with the best sum rate scored (DDPM.sample_best); 1 is the reference's single draw.
     `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
+    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
+    single-setting spelling and are not read then."""
     _, _, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
@@ -112,12 +114,14 @@ def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batc
     diffusion_model.to(device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
+    if variants is not None and repeats < 2:
+        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
     X = torch.tensor(X_test, dtype=torch.float32)
     if repeats > 1:
         Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
         Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
         from .decode import msr_rate
-        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan).objective
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants).objective
         true_rate = msr_rate(Yt, Xt)
         out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
                "avg_rate_diff": float(torch.mean(pred_rate - true_rate)), "repeats": int(repeats)}

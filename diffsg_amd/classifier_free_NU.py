@@ -107,10 +107,12 @@ def rate_calc(Y_pred_decoded, X):
 
 @torch.no_grad()
 def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, width=400, height=400,
-                 log=print, repeats=1, steps=None, sampler="strided", eta=0.0):
+                 log=print, repeats=1, steps=None, sampler="strided", eta=0.0, variants=None):
     """classifier_free_NU.py:306-361.  `repeats` > 1: that many draws per test row, the one with the best rate scored
     (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference."""
+    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
+    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
+    single-setting spelling and are not read then."""
     _, _, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
     device = _device()
@@ -119,6 +121,8 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
     diffusion_model.to(device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
+    if variants is not None and repeats < 2:
+        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
     X = torch.tensor(X_test, dtype=torch.float32)
     # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
     # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
@@ -137,7 +141,7 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
     Yt[:, 2:] *= P_sum
     if repeats > 1:
         # width / height of THIS call, as custom_decoder below gets them (the hook reads the model's custom_config: the same values)
-        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan).objective
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants).objective
     else:
         pred_rate = rate_calc(custom_decoder(Y_pred, width, height, P_sum), Xt)
     true_rate = rate_calc(Yt, Xt)

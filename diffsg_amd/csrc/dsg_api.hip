@@ -264,6 +264,13 @@ struct dsg_handle {
     // chunked calls (dsg_sample_chunked): per-chunk Philox seeds and per-chunk renorm partials
     DevBuf<unsigned long long> seeds_dev; int seeds_cap = 0;
     DevBuf<double> red_chunks; int red_chunks_cap = 0;
+    // dsg_set_chunk_variants: per-chunk omega / renorm count / table index of a chunked call; var_chunks == 0: none held.  The buffers only grow
+    // and are kept when the setting is removed.  The step graphs of the variant form hold `var_call` alone (one block, allocated once), never
+    // these buffers: k_set_var writes their addresses into it per call.
+    DevBuf<float> var_omega; DevBuf<int> var_renorm, var_table; int var_cap = 0;
+    int var_chunks = 0, var_tables = 1; bool var_has_renorm = false, var_has_table = false;
+    std::vector<int> var_renorm_host;            // the counts, for the checks a call makes before it enqueues anything
+    DevBuf<VarParams> var_call;
 
     // training workspace
     size_t tr_per_tile = 0;      // floats per tile
@@ -311,6 +318,10 @@ struct dsg_handle {
     // captured reverse steps of the current workspace shape: gexec[0] = one early (renorm) step, gexec[1 + k] = 2^k later steps
     GraphExec gexec[1 + 6];
     int g_rows = -1, g_chunks = -1, g_chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
+    // the same set for calls with chunk variants (k_update_var, k_renorm_apply_var), cached BESIDE the plain one under its own key: plain and
+    // variants calls alternating on one handle replay their own graphs
+    GraphExec gexec_var[1 + 6];
+    int gv_rows = -1, gv_chunks = -1, gv_chunk_rows = -1;
 };
 
 namespace {
@@ -460,7 +471,9 @@ void carve(dsg_handle* h) {
 
 void free_graphs(dsg_handle* h) {
     for (auto& g : h->gexec) g.reset();
+    for (auto& g : h->gexec_var) g.reset();
     h->g_rows = h->g_chunks = h->g_chunk_rows = -1;
+    h->gv_rows = h->gv_chunks = h->gv_chunk_rows = -1;
 }
 
 constexpr int kMaxGmax = 256;   // distinct gradient tensors whose max|G| is tracked (3 per block + 1 per Linear)
@@ -2375,6 +2388,37 @@ int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_step
     return 0;
 }
 
+int dsg_set_chunk_variants(dsg_handle* h, const float* omega_host, const int* renorm_host, const int* table_host, int chunks, int tables) {
+    if (!h) return fail("null handle");
+    if (chunks < 0) return fail("dsg_set_chunk_variants: chunks = %d is negative", chunks);
+    if (!omega_host || chunks == 0) { h->var_chunks = 0; return 0; }     // nothing is overwritten: an enqueued call keeps reading the buffers
+    if (tables < 1) return fail("dsg_set_chunk_variants: tables = %d, at least one coefficient table is needed", tables);
+    for (int c = 0; c < chunks; ++c) {
+        if (table_host && (table_host[c] < 0 || table_host[c] >= tables))
+            return fail("dsg_set_chunk_variants: chunk %d names table %d, outside 0 .. %d", c, table_host[c], tables - 1);
+        if (renorm_host && renorm_host[c] < 0) return fail("dsg_set_chunk_variants: chunk %d has a negative renorm count (%d)", c, renorm_host[c]);
+    }
+    DeviceGuard dg(h);
+    // an enqueued call may still read the old values; the step graphs of the variant form do not hold these buffers and stay
+    HIPCK(hipDeviceSynchronize());
+    if (!h->var_call) HIPCK(h->var_call.alloc(1));
+    if (chunks > h->var_cap) {
+        h->var_chunks = 0; h->var_cap = 0;
+        HIPCK(h->var_omega.alloc((size_t)chunks));
+        HIPCK(h->var_renorm.alloc((size_t)chunks));
+        HIPCK(h->var_table.alloc((size_t)chunks));
+        h->var_cap = chunks;
+    }
+    HIPCK(hipMemcpy(h->var_omega, omega_host, (size_t)chunks * sizeof(float), hipMemcpyHostToDevice));
+    if (renorm_host) HIPCK(hipMemcpy(h->var_renorm, renorm_host, (size_t)chunks * sizeof(int), hipMemcpyHostToDevice));
+    if (table_host) HIPCK(hipMemcpy(h->var_table, table_host, (size_t)chunks * sizeof(int), hipMemcpyHostToDevice));
+    h->var_renorm_host.clear();
+    if (renorm_host) h->var_renorm_host.assign(renorm_host, renorm_host + chunks);
+    h->var_has_renorm = renorm_host != nullptr; h->var_has_table = table_host != nullptr;
+    h->var_chunks = chunks; h->var_tables = tables;
+    return 0;
+}
+
 int dsg_set_option(dsg_handle* h, int option, int value) {
     if (!h) return fail("null handle");
     DeviceGuard dg(h);
@@ -2472,7 +2516,7 @@ int dsg_unet_forward(dsg_handle* h, const float* x, const float* t, const float*
 // (a rank whose graphs are already cached would not issue it: the all-reduces would pair up wrongly or hang) and the caller's
 // `renorm_stats` pointer would be baked into the cached graph and outlive the hook.
 static int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, bool renorm, hipStream_t s,
-                        const Event* ev = nullptr, bool use_hook = true, int chunks = 1, size_t chunk_n = 0) {
+                        const Event* ev = nullptr, bool use_hook = true, int chunks = 1, size_t chunk_n = 0, bool var = false) {
     if (ev) {  // DSG_SAMPLE_PROFILE: one event pair per operator launch
         const bool fuse = h->fuse_hi - h->fuse_lo >= 2;
         bool skip_next = false;
@@ -2493,8 +2537,16 @@ static int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, boo
     const unsigned ublocks = (unsigned)(((u.n + 3) / 4 + 255) / 256 < 2048 ? ((u.n + 3) / 4 + 255) / 256 : 2048);
     UpdateArgs ua = u;
     ua.record_y = renorm ? 0 : 1;
-    hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(256), 0, s, ua);
-    if (renorm && h->renorm_fn && use_hook) {
+    if (var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
+    else hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(256), 0, s, ua);
+    if (renorm && var) {   // chunk variants (never with a hook): every chunk's sums, then the apply of the chunks whose count covers this step
+        double* p1 = chunks > 1 ? h->red_chunks : h->red;
+        double* p2 = chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks;
+        const size_t cn = chunks > 1 ? chunk_n : (size_t)0;
+        hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, chunks), dim3(256), 0, s, (const float*)u.y, u.n, p1, p2, cn);
+        hipLaunchKernelGGL(k_renorm_apply_var, dim3(kRedBlocks, chunks), dim3(256), 0, s, u.y, u.n, (const double*)p1, (const double*)p2, cn,
+                           (const CallParams*)u.cp, (const int*)u.step_ptr, (const VarParams*)h->var_call);
+    } else if (renorm && h->renorm_fn && use_hook) {
         // sharded call that standardises with the statistics of the WHOLE batch (MSR.py:136-137 on the concatenation of all
         // ranks' rows): local moments -> the caller's all-reduce of 3 doubles (enqueued on this stream) -> apply
         hipLaunchKernelGGL(k_renorm_moments, dim3(kRedBlocks), dim3(256), 0, s, u.y, u.n, h->red, h->red + kRedBlocks);
@@ -2539,6 +2591,25 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     if (chunk_rows > 0 && (chunk_rows % 32 != 0)) return fail("dsg_sample_chunked: chunk_rows must be a multiple of 32 (a row tile)");
     if (chunks > 1 && h->renorm_fn) return fail("dsg_sample_chunked: a renorm hook (sharded global renorm) and chunking exclude each other");
     if (chunks > 1 && !seeds_host && !(y_T && (noise || T <= 2))) return fail("dsg_sample_chunked: per-chunk seeds are required");
+    // chunk variants (dsg_set_chunk_variants): every check before anything is enqueued or allocated
+    const bool var = h->var_chunks > 0;
+    const int n_default = h->grid_n ? h->grid_renorm : (T < 4 ? T : 4);  // steps i > T-5 (MSR.py:136), or dsg_set_step_grid's count
+    int n_renorm = n_default;
+    if (var) {
+        if (chunk_rows <= 0)
+            return fail("dsg_sample: the handle holds chunk variants (dsg_set_chunk_variants) for %d chunk(s): call dsg_sample_chunked, or remove them", h->var_chunks);
+        if (chunks != h->var_chunks)
+            return fail("dsg_sample_chunked: the handle holds variants for %d chunk(s) (dsg_set_chunk_variants), the call has %d", h->var_chunks, chunks);
+        if (h->renorm_fn) return fail("dsg_sample_chunked: a renorm hook (sharded global renorm) and chunk variants exclude each other");
+        if (h->var_has_renorm) {
+            n_renorm = 0;
+            for (int c = 0; c < chunks; ++c) {
+                const int r = h->var_renorm_host[c];
+                if (r > T) return fail("dsg_sample_chunked: chunk %d has a renorm count of %d (dsg_set_chunk_variants), the call has T = %d steps", c, r, T);
+                if (r > n_renorm) n_renorm = r;
+            }
+        }
+    }
     if (ensure_workspace(h, B, T)) return 1;
     const int D = h->d.input_dim, CG = groups_of(h->d.cond_dim), tpp = cdiv(B, 32);
     const size_t n = (size_t)B * D;
@@ -2576,6 +2647,10 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     // to the device as kernel arguments: no pageable copy, no synchronise - consecutive calls pipeline on the stream
     const CallParams cp{noise, coef, omega, T, seed, rec_y, rec_eps, chunk_n / 4, chunks > 1 ? h->seeds_dev : nullptr};
     hipLaunchKernelGGL(k_set_call, dim3(1), dim3(64), 0, s, h->step_dev, h->call_dev.get(), cp, T);
+    if (var) {   // with variants `coef` is [tables][T][4] and `omega` is not read
+        const VarParams vp{h->var_omega, h->var_has_renorm ? h->var_renorm.get() : nullptr, h->var_has_table ? h->var_table.get() : nullptr, n_default};
+        hipLaunchKernelGGL(k_set_var, dim3(1), dim3(64), 0, s, h->var_call.get(), vp);
+    }
 
     RunCtx c{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true};
     c.advance_step = h->step_dev;
@@ -2584,7 +2659,6 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
-    const int n_renorm = h->grid_n ? h->grid_renorm : (T < 4 ? T : 4);  // steps i > T-5 (MSR.py:136), or dsg_set_step_grid's count
     if (flags & DSG_SAMPLE_PROFILE) {
         const size_t nops = h->ops.size();
         h->op_ms.assign(nops, 0.0);
@@ -2592,32 +2666,37 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         std::vector<Event> ev(2 * nops);
         for (auto& e : ev) HIPCK(hipEventCreate(e.put()));
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, k < n_renorm, s, ev.data(), true, chunks, chunk_n)) return 1;
+            if (enqueue_step(h, c, u, k < n_renorm, s, ev.data(), true, chunks, chunk_n, var)) return 1;
     } else if (flags & DSG_SAMPLE_NO_GRAPH) {
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, k < n_renorm, s, nullptr, true, chunks, chunk_n)) return 1;
+            if (enqueue_step(h, c, u, k < n_renorm, s, nullptr, true, chunks, chunk_n, var)) return 1;
     } else {
         // The step index is a device counter and everything per call sits in device memory, so a captured step depends only on
         // the workspace (rows, chunk count) -- not on T, the seed or the schedule.  Captured once per workspace: one early
         // (renorm) step and runs of 1, 2, 4 ... 32 later steps; a call replays min(T, 4) early steps and the binary
         // decomposition of the rest (the shipped T = 20: 4 + one 16-step graph = 5 launches for the whole reverse loop).
-        if (!(h->g_rows == B && h->g_chunks == chunks && h->g_chunk_rows == chunk_rows)) {
-            free_graphs(h);
-            h->g_rows = B; h->g_chunks = chunks; h->g_chunk_rows = chunk_rows;
+        // two sets, one per form of the step (plain / chunk variants), each under its own key: a change of shape drops its own set only
+        GraphExec* const gexec = var ? h->gexec_var : h->gexec;
+        int& g_rows = var ? h->gv_rows : h->g_rows;
+        int& g_chunks = var ? h->gv_chunks : h->g_chunks;
+        int& g_chunk_rows = var ? h->gv_chunk_rows : h->g_chunk_rows;
+        if (!(g_rows == B && g_chunks == chunks && g_chunk_rows == chunk_rows)) {
+            for (int k = 0; k < 1 + kStepRunGraphs; ++k) gexec[k].reset();
+            g_rows = B; g_chunks = chunks; g_chunk_rows = chunk_rows;
         }
         // captured lazily: only the run lengths a call replays (a one-off batch size pays for its own decomposition, not for
         // 64 steps of nodes)
         auto graph_of = [&](int variant) -> int {
-            if (h->gexec[variant]) return 0;
+            if (gexec[variant]) return 0;
             const int run = variant == 0 ? 1 : 1 << (variant - 1);
             hipGraph_t g = nullptr;
             HIPCK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = 0;
-            for (int k = 0; k < run && !rc; ++k) rc = enqueue_step(h, c, u, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false, chunks, chunk_n);
+            for (int k = 0; k < run && !rc; ++k) rc = enqueue_step(h, c, u, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false, chunks, chunk_n, var);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
-            e = hipGraphInstantiate(h->gexec[variant].put(), g, nullptr, nullptr, 0);
+            e = hipGraphInstantiate(gexec[variant].put(), g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (e != hipSuccess) return fail("hipGraphInstantiate: %s", hipGetErrorString(e));
             return 0;
@@ -2627,14 +2706,14 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
                 if (enqueue_step(h, c, u, true, s)) return 1;
             } else {
                 if (graph_of(0)) return 1;
-                HIPCK(hipGraphLaunch(h->gexec[0], s));
+                HIPCK(hipGraphLaunch(gexec[0], s));
             }
         }
         for (int left = T - n_renorm; left > 0;) {
             int v = kStepRunGraphs - 1;
             while ((1 << v) > left) --v;
             if (graph_of(1 + v)) return 1;
-            HIPCK(hipGraphLaunch(h->gexec[1 + v], s));
+            HIPCK(hipGraphLaunch(gexec[1 + v], s));
             left -= 1 << v;
         }
     }

@@ -1243,6 +1243,67 @@ __global__ __launch_bounds__(256) void k_update(const UpdateArgs a) {
     }
 }
 
+// Chunk variants (dsg_set_chunk_variants): every chunk of a chunked call has its own omega, its own coefficient table out of
+// `tables` stacked ones (cp.coef is then [tables][T][4]) and its own number of early renormalised steps.  Like CallParams the block lives in
+// device memory and is written per call (k_set_var), so that the captured step graphs of the variant form depend on none of it.
+struct VarParams {
+    const float* omega;   // device [chunks]
+    const int* renorm;    // device [chunks], or null: `renorm_default` for every chunk
+    const int* table;     // device [chunks], or null: table 0 for every chunk
+    int renorm_default;   // the call's own count: min(T, 4), or dsg_set_step_grid's
+};
+__global__ void k_set_var(VarParams* dst, const VarParams vp) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = vp;
+}
+
+// k_update with the setting of the quad's chunk (a chunk is a multiple of 32 rows, so a quad never straddles chunks): the same
+// expressions in the same order, the same Philox stream (`step`) and chunk-local index, the same injected-noise row T-1-step -- read iff
+// THIS chunk's c4 != 0 --, the 16-byte quad path and the scalar path.  A chunk's result is the bits of its own sample() call.  A variants
+// call never records the trajectory (dsg_sample_rec refuses while variants are held), so the record stores are not here.
+__global__ __launch_bounds__(256) void k_update_var(const UpdateArgs a, const VarParams* __restrict__ vpp) {
+    const int step = *a.step_ptr;
+    const CallParams cp = *a.cp;
+    const VarParams vp = *vpp;
+    const size_t n4 = (a.n + 3) / 4;
+    const float* zbase = cp.z ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;   // dereferenced by noisy chunks only (rows exist for step >= 2)
+    const bool quads = (a.n & 3) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zbase)) & 15) == 0;
+    for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
+        const size_t c = cp.chunk_n4 ? i4 / cp.chunk_n4 : 0;
+        const float* row = cp.coef + ((size_t)(vp.table ? vp.table[c] : 0) * cp.T + step) * 4;
+        const float c1 = row[0], c2 = row[1], c3 = row[2];
+        const bool noisy = row[3] != 0.f;
+        const float omega = vp.omega[c], w1 = 1.0f + omega;
+        const float* zrow = noisy ? zbase : nullptr;
+        float zz[4] = {0.f, 0.f, 0.f, 0.f};
+        if (noisy && !zrow) { unsigned long long sd; size_t li; chunk_of(cp, i4, sd, li); normal4(sd, (uint32_t)step, li, zz); }
+        if (quads) {
+            const float4 e0 = ld4(a.eps + i4 * 4), e1 = ld4(a.eps + a.n + i4 * 4), yv = ld4(a.y + i4 * 4);
+            if (zrow) { const float4 zv = ld4(zrow + i4 * 4); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
+            const float e0a[4] = {e0.x, e0.y, e0.z, e0.w}, e1a[4] = {e1.x, e1.y, e1.z, e1.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
+            float out[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const float e = __fsub_rn(__fmul_rn(w1, e1a[p]), __fmul_rn(omega, e0a[p]));
+                const float v = __fmul_rn(__fsub_rn(ya[p], __fmul_rn(c1, e)), c2);
+                out[p] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
+            }
+            st4(a.y + i4 * 4, make_float4(out[0], out[1], out[2], out[3]));
+            continue;
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const size_t i = i4 * 4 + p;
+            if (i < a.n) {
+                if (zrow) zz[p] = zrow[i];
+                const float e = __fsub_rn(__fmul_rn(w1, a.eps[a.n + i]), __fmul_rn(omega, a.eps[i]));
+                const float v = __fmul_rn(__fsub_rn(a.y[i], __fmul_rn(c1, e)), c2);
+                a.y[i] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
+            }
+        }
+    }
+}
+
 // y_T ~ N(0, 1) on device (throughput mode; the reference draws it on the host, MSR.py:115)
 __global__ void k_randn(float* __restrict__ y, size_t n, unsigned long long seed, unsigned stream) {
     const size_t n4 = (n + 3) / 4;
@@ -1376,6 +1437,31 @@ __global__ __launch_bounds__(256) void k_renorm_apply(float* y, size_t n, const 
         y[i] = o;
         if (rec) rec[i] = o;
     }
+}
+
+// Chunk variants: k_renorm_apply behind a predicate on the chunk.  Chunk c = blockIdx.y standardises on the first renorm[c] steps of the call,
+// the device step indices i > T-1-renorm[c], from the statistics k_renorm_sum left for it (same grid, strides and order as k_renorm_apply:
+// the bits of the chunk's own call); on the other steps its elements are not touched (its sums were formed and are dropped).
+__global__ __launch_bounds__(256) void k_renorm_apply_var(float* y, size_t n, const double* __restrict__ part, const double* __restrict__ part2,
+                                                          size_t chunk_n, const CallParams* __restrict__ cp, const int* __restrict__ step_ptr,
+                                                          const VarParams* __restrict__ vp) {
+    const int count = vp->renorm ? vp->renorm[blockIdx.y] : vp->renorm_default;
+    if (!(*step_ptr > cp->T - 1 - count)) return;       // uniform over the block
+    { const float* yc = y; renorm_chunk(yc, n, chunk_n); y = const_cast<float*>(yc); }
+    part += (size_t)blockIdx.y * kRedBlocks; part2 += (size_t)blockIdx.y * kRedBlocks;
+    double tot = 0.0, tot2 = 0.0;
+    for (int i = 0; i < kRedBlocks; ++i) { tot += part[i]; tot2 += part2[i]; }
+    const double mean_d = tot / (double)n;
+    const float mean = (float)mean_d;
+    const double var = (tot2 - tot * mean_d) / (double)(n - 1);
+    const float sd = sqrtf((float)(var > 0.0 ? var : 0.0));
+    const size_t n4 = (reinterpret_cast<uintptr_t>(y) & 15) ? 0 : n / 4;
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x, st = (size_t)gridDim.x * blockDim.x;
+    for (size_t i4 = t; i4 < n4; i4 += st) {
+        const float4 v = ld4(y + 4 * i4);
+        st4(y + 4 * i4, make_float4((v.x - mean) / sd, (v.y - mean) / sd, (v.z - mean) / sd, (v.w - mean) / sd));
+    }
+    for (size_t i = 4 * n4 + t; i < n; i += st) y[i] = (y[i] - mean) / sd;
 }
 
 // EMA (ema.py:11-12): avg = decay*avg + (1-decay)*p over one flat range

@@ -144,13 +144,26 @@ class DDPMCore(nn.Module):
             raise ValueError(f"step plan: {K} taus need t of shape ({K},) and coef of shape ({K}, 4)")
         if not 0 <= int(plan.renorm_steps) <= K:
             raise ValueError(f"step plan: renorm_steps = {plan.renorm_steps} is outside 0 .. {K}")
-        if bool((plan.coef[:2, 3] != 0).any()):
+        if not self._coef_noise_free(plan.coef):
             raise ValueError("step plan: steps 0 and 1 must be noise free (coef[:2, 3] == 0): the noise tensor has K - 2 rows")
         if noise is not None:
             want = (max(K - 2, 0), cond.shape[0], self.model.cfg["input_dim"])
             if tuple(noise.shape) != want:
                 raise ValueError(f"noise must have shape {want} for a plan of {K} steps")
         return K
+
+    def _coef_noise_free(self, coef):
+        """coef[:2, 3] == 0, remembered per tensor (and version): the table may live on the device, where the answer costs a synchronise --
+        once per table, not once per call or, with variants, once per chunk."""
+        seen = self.__dict__.setdefault("_coef_checked", [])
+        for c, v in seen:
+            if c is coef and v == coef._version:
+                return True
+        if bool((coef[:2, 3] != 0).any()):
+            return False
+        seen.append((coef, coef._version))
+        del seen[:-16]
+        return True
 
     def _use_plan(self, hd, plan, dev):
         """Make handle `hd` hold `plan`'s step grid (none for plan=None) and return the plan's coefficient table on `dev`.  What the
@@ -180,6 +193,83 @@ class DDPMCore(nn.Module):
         nat.step_grid = (hd, plan, coef)
         return coef
 
+    def _resolve_variants(self, variants, cond, noise):
+        """[(omega, plan)] of a list of variants with `None` plans replaced by the identity plan (all T trained steps, the trained table's
+        own rows, min(T, 4) renorm steps), and the step count K they share -- after the checks that need no device: every plan passes
+        `_plan_steps`, and all of them have the first one's `taus` and `t` (one time table per call)."""
+        from .steps import StepPlan, strided
+        variants = list(variants)
+        if not variants:
+            raise ValueError("variants: at least one (omega, plan) is needed")
+        out, ident = [], None
+        for k, v in enumerate(variants):
+            try:
+                omega, plan = v
+            except (TypeError, ValueError):
+                raise ValueError(f"variant {k} is not an (omega, plan) pair") from None
+            if plan is None:
+                ident = plan = ident if ident is not None else strided(self, self.T)
+            elif not isinstance(plan, StepPlan):
+                raise ValueError(f"variant {k}: the plan must be a steps.StepPlan or None")
+            try:
+                self._plan_steps(plan, cond, noise)
+            except ValueError as e:
+                raise ValueError(f"variant {k}: {e}") from None
+            first = out[0][1] if out else plan
+            if not ((plan.taus is first.taus or tuple(plan.taus) == tuple(first.taus)) and (plan.t is first.t or torch.equal(plan.t.cpu(), first.t.cpu()))):
+                raise ValueError(f"variant {k} has another step grid (taus / t) than variant 0: the variants of one call share the time "
+                                 "table and may differ in omega, coef and renorm_steps")
+            out.append((float(omega), plan))
+        return out, len(out[0][1].taus)
+
+    def _use_variants(self, hd, chunks, dev):
+        """Make handle `hd` hold the per-chunk settings `chunks` = [(omega, plan)], one per chunk (None: remove them) and, with them, the
+        step grid they share; returns the stacked coefficient tables [tables][K][4] on `dev`.  What the handle holds is remembered beside
+        it, as `_use_plan` does: repeated calls with the same variants set nothing (setting them synchronises the device)."""
+        import ctypes
+        nat = self.model._native
+        held = getattr(nat, "chunk_variants", None)          # (handle, key)
+        if held is not None and held[0] != hd:
+            held = None
+        if chunks is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_chunk_variants(hd, None, None, None, 0, 1))
+                nat.chunk_variants = None
+            return None
+        plan0 = chunks[0][1]
+        if _is_trained_grid(plan0, self.T):
+            self._use_plan(hd, None, dev)                     # all T trained steps at t = i / T: the plan-less time table
+        else:
+            grid = getattr(nat, "step_grid", None)
+            if not (grid is not None and grid[0] == hd and torch.equal(grid[1].t, plan0.t)):   # the renorm count of the grid is not read
+                self._use_plan(hd, plan0, dev)
+        # the distinct coefficient tensors, stacked once
+        coefs, table = [], []
+        for _, p in chunks:
+            for j, c in enumerate(coefs):
+                if c is p.coef:
+                    break
+            else:
+                j = len(coefs)
+                coefs.append(p.coef)
+            table.append(j)
+        cache = getattr(self, "_var_tables", None)
+        if cache is not None and cache[1] == dev and len(cache[0]) == len(coefs) and all(a is b for a, b in zip(cache[0], coefs)):
+            stacked = cache[2]
+        else:
+            stacked = torch.stack([c.detach().to(dev, torch.float32) for c in coefs]).contiguous()
+            self._var_tables = (coefs, dev, stacked)
+        key = (tuple(np.float32(o).item() for o, _ in chunks), tuple(int(p.renorm_steps) for _, p in chunks), tuple(table), len(coefs))
+        if held is None or held[1] != key:
+            n = len(chunks)
+            om = (ctypes.c_float * n)(*key[0])
+            rn = (ctypes.c_int * n)(*key[1])
+            tb = (ctypes.c_int * n)(*key[2])
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().dsg_set_chunk_variants(hd, om, rn, tb, n, len(coefs)))
+            nat.chunk_variants = (hd, key)
+        return stacked
+
     def _sample_once(self, cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan=None):
         hd = self.model.native_handle()
         B, D, T = cond.shape[0], self.model.cfg["input_dim"], (self.T if plan is None else len(plan.taus))
@@ -201,6 +291,7 @@ class DDPMCore(nn.Module):
         rec = torch.empty(2, T, B, D, device=dev, dtype=torch.float32) if self.record_denoise_path else None
         if B == 0:
             return out                     # no rows, nothing to launch (the reference's loop runs on empty tensors)
+        self._use_variants(hd, None, dev)  # a sample() call is no chunked call: per-chunk settings of an earlier one go
         coef = self._use_plan(hd, plan, dev)
         flags = 2 if profile else (0 if use_graph else 1)
         # T <= 2 has no noisy step (MSR.py:129): a null pointer (= device Philox) is then never dereferenced
@@ -222,14 +313,28 @@ class DDPMCore(nn.Module):
 
     @torch.no_grad()
     def sample_chunked(self, cond, omega=1.0, chunk_rows=512, *, seeds=None, y_T=None, noise=None, use_graph=True, check_range=True,
-                       plan=None):
+                       plan=None, variants=None):
         """The reference's evaluation shape in one set of launches: `cond` is sampled as consecutive `chunk_rows`-row slices, each
         an independent `sample()` call (own start state and noise, own early-step renorm statistics; classifier_free_MSR.py:257,
         273-279).  Row for row bit-identical to `torch.cat([self.sample(cond[i:i + chunk_rows], omega, seed=seeds[k]) ...])`,
         `seeds` = one Philox seed per chunk (default: drawn from torch's global generator, one per chunk, in chunk order).
-        `plan`: as in `sample`, the same plan for every chunk."""
+        `plan`: as in `sample`, the same plan for every chunk.
+        `variants`: one `(omega, plan)` per chunk (plan None: all T trained steps) instead of `omega` and `plan` -- chunk k is then
+        `self.sample(cond[...], omega_k, seed=seeds[k], plan=plan_k)` bit for bit.  The plans of one call share `taus` and `t` and may
+        differ in `coef` and `renorm_steps` (`steps.with_renorm`); DESIGN.md 15."""
         import ctypes
-        K = self._plan_steps(plan, cond, noise)
+        if variants is not None:
+            if plan is not None:
+                raise ValueError("sample_chunked: give the plans inside `variants`, not as `plan`")
+            variants, K = self._resolve_variants(variants, cond, noise)
+            want = max(1, -(-cond.shape[0] // int(chunk_rows))) if chunk_rows > 0 else 0
+            if len(variants) != want:
+                raise ValueError(f"sample_chunked: {want} chunk(s) of {chunk_rows} rows need {want} variants, got {len(variants)}")
+            if self.record_denoise_path:
+                raise RuntimeError("DDPM.sample_chunked: a call with variants does not record the de-noising trajectory: call sample() per "
+                                   "chunk (record_denoise_path is set)")
+        else:
+            K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
             raise RuntimeError("DDPM.sample_chunked: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
         B, D, T = cond.shape[0], self.model.cfg["input_dim"], K
@@ -237,6 +342,8 @@ class DDPMCore(nn.Module):
             raise ValueError("chunk_rows must be a multiple of 32")
         nch = (B + chunk_rows - 1) // chunk_rows
         if nch <= 1:
+            if variants is not None:                 # one chunk: its own call
+                omega, plan = variants[0]
             return self.sample(cond, omega, y_T=y_T, noise=noise, seed=None if seeds is None else int(seeds[0]), use_graph=use_graph,
                                check_range=check_range, plan=plan)
         if self.record_denoise_path:
@@ -265,7 +372,11 @@ class DDPMCore(nn.Module):
             nonlocal coef
             o = torch.empty(B, D, device=dev, dtype=torch.float32)
             hd = self.model.native_handle()
-            coef = self._use_plan(hd, plan, dev)
+            if variants is None:
+                self._use_variants(hd, None, dev)
+                coef = self._use_plan(hd, plan, dev)
+            else:
+                coef = self._use_variants(hd, variants, dev)      # [tables][K][4]; `omega` is not read by the call
             with torch.cuda.device(dev):
                 _lib.check(_lib.lib().dsg_sample_chunked(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, sd, int(chunk_rows),
                                                          float(omega), _lib.ptr(coef), T, _lib.ptr(o), B, 0 if use_graph else 1,
@@ -310,7 +421,7 @@ class DDPMCore(nn.Module):
 
     @torch.no_grad()
     def sample_best(self, cond, X, n, omega=1.0, *, seeds=None, chunk_rows=None, max_rows=65536, use_graph=True, check_range=True,
-                    return_objectives=False, plan=None):
+                    return_objectives=False, plan=None, variants=None):
         """Repeated sampling: `n` rounds of `sample(cond, omega)` (of `sample_chunked(cond, omega, chunk_rows)` when `chunk_rows`
         is given), each decoded and scored against the unscaled features `X`, the best round kept per condition
         (`repeated.best_of`; returns its `BestOf`).
@@ -319,8 +430,23 @@ class DDPMCore(nn.Module):
         per chunk per round with `chunk_rows`, round-major (default: drawn from torch's global generator in that order).
         Where the rounds tile into whole 32-row-aligned chunks they are sampled in groups: `cond` is repeated for as many
         rounds as keep the launch at or below `max_rows` rows (at least one) and ONE `sample_chunked` call samples the group,
-        row for row bit-identical to the rounds' own calls.  Raw candidates of at most one group are alive at a time."""
+        row for row bit-identical to the rounds' own calls.  Raw candidates of at most one group are alive at a time.
+
+        `variants`: a list (any length >= 1) of `(omega, plan)` sampler settings instead of `omega` and `plan`: round r runs
+        `variants[r % len(variants)]`, every chunk of the round with that setting, so `BestOf.round % len(variants)` is the winning
+        variant.  The grouping changes nothing: grouped rounds in one chunked call (per-chunk settings), one call per
+        round and the serial off-tile path give the same `BestOf` bit for bit.  The plans share `taus` and `t` (`sample_chunked`)."""
         from .repeated import best_of
+        if variants is not None:
+            if plan is not None:
+                raise ValueError("sample_best: give the plans inside `variants`, not as `plan`")
+            if int(n) < 1:
+                raise ValueError("sample_best: n must be at least 1")
+            variants = list(variants)
+            self._resolve_variants(variants, cond, None)
+            if self.record_denoise_path:
+                raise RuntimeError("DDPM.sample_best: variants and record_denoise_path exclude each other (a grouped call records no "
+                                   "trajectory)")
         if not cond.is_cuda:
             raise RuntimeError("DDPM.sample_best: `cond` is not on a HIP device; libdiffsg_hip has no CPU path")
         n = int(n)
@@ -342,8 +468,14 @@ class DDPMCore(nn.Module):
         running = None
         for r0 in range(0, n, group):
             g = min(group, n - r0)
+            if variants is not None and not (grouped and g > 1):      # a group of one round: that round's own setting, its own call(s)
+                omega, kw["plan"] = variants[r0 % len(variants)]
             sd = seeds[r0 * per_round:(r0 + g) * per_round]
-            if grouped and g > 1:
+            if variants is not None and grouped and g > 1:
+                per_chunk = [variants[(r0 + k) % len(variants)] for k in range(g) for _ in range(per_round)]
+                Y = self.sample_chunked(cond.repeat(g, 1), 0.0, u, seeds=sd, use_graph=use_graph, check_range=check_range,
+                                        variants=per_chunk).view(g, B, -1)
+            elif grouped and g > 1:
                 Y = self.sample_chunked(cond.repeat(g, 1), omega, u, seeds=sd, **kw).view(g, B, -1)
             elif one_call:
                 Y = self.sample(cond, omega, seed=sd[0], **kw)[None]
@@ -579,6 +711,10 @@ class DDPMCore(nn.Module):
             else:                                   # gloo has no AVG
                 dist.all_reduce(self._grad_bucket, op=dist.ReduceOp.SUM)
                 self._grad_bucket.div_(dist.get_world_size())
+
+
+def _is_trained_grid(plan, T):
+    return tuple(plan.taus) == tuple(range(T)) and torch.equal(plan.t.cpu(), torch.arange(T) / T)
 
 
 def _dp_rank():

@@ -6,7 +6,7 @@ A `StepPlan` is what a `DDPM.sample(..., plan=...)` call needs beyond the model:
     y <- (y - c1 * eps) * c2 + c3 * z,        z used iff c4 != 0
 
 and how many of the first steps of a call standardise y (`renorm_steps`; classifier_free_MSR.py:136-137).  Step index K-1 runs first,
-0 last.  Three constructors:
+0 last.  Three constructors (and `with_renorm(plan, n)`: the same plan with another renorm count):
 
   strided(ddpm, K)     K < T steps of the reference's own (ancestral) update rule, re-derived for the sub-sequence;
   ddim(ddpm, K, eta)   DDIM (Song et al. 2021, eq. 12) on the same grid; deterministic at eta = 0;
@@ -116,6 +116,15 @@ def tail(ddpm, k, renorm_steps=0):
         raise ValueError(f"tail: renorm_steps must be in [0, {k + 1}], got {renorm_steps}")
     taus = tuple(range(k + 1))
     return StepPlan(taus, _times(taus, T), ddpm._coef_table()[:k + 1], int(renorm_steps))
+
+
+def with_renorm(plan_or_ddpm, renorm_steps):
+    """The plan with `renorm_steps` early renormalised steps (0 .. K) and everything else shared; for a `DDPM` the identity plan -- all T
+    trained steps, the trained table's own rows -- with that count.  What a chunk variant varies besides omega and the table."""
+    plan = plan_or_ddpm if isinstance(plan_or_ddpm, StepPlan) else strided(plan_or_ddpm, plan_or_ddpm.T)
+    if int(renorm_steps) != renorm_steps or not 0 <= int(renorm_steps) <= plan.K:
+        raise ValueError(f"with_renorm: renorm_steps must be an integer in [0, {plan.K}], got {renorm_steps}")
+    return StepPlan(plan.taus, plan.t, plan.coef, int(renorm_steps))
 
 
 def make(ddpm, steps=None, sampler="strided", eta=0.0):

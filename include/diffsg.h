@@ -186,6 +186,27 @@ int dsg_sample_chunked(dsg_handle* h, const float* cond, const float* y_T, const
  * the grid does not synchronise.  The captured step graphs do not depend on the grid and are kept. */
 int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_steps);
 
+/* Chunk variants: a per-chunk sampler setting for dsg_sample_chunked.  Every chunk of a chunked call is an independent sample() call; with
+ * this per-handle setting the calls may also differ in omega, in the coefficient table and in the number of early renormalised steps:
+ *   omega_host   HOST array [chunks]: chunk c is guided with omega_host[c];
+ *   renorm_host  HOST array [chunks]: chunk c standardises y, with its own statistics, on the FIRST renorm_host[c] steps of the call (step
+ *                indices i > T-1-renorm_host[c]) and is left alone on the others; NULL: the call's default count for every chunk
+ *                (min(T, 4), or dsg_set_step_grid's);
+ *   table_host   HOST array [chunks] of indices 0 .. tables-1; NULL: table 0 for every chunk.
+ * chunks == 0 or omega_host == NULL removes the setting.  Refused: chunks < 0, tables < 1, a table index outside 0 .. tables-1, a negative
+ * renorm count.  While the setting is held
+ *   - dsg_sample_chunked reads `coef` as device [tables][T][4] (chunk c uses rows table_host[c] * T ...), ignores its `omega` argument and
+ *     fails before anything is enqueued when ceil(B / chunk_rows) != chunks or a renorm count exceeds T; chunks == 1 with
+ *     chunk_rows >= B is legal; the time values are one per call (dsg_set_step_grid): the variants share the step grid;
+ *   - chunk c's rows are bit-identical to dsg_sample on its slice with omega_host[c], table table_host[c], seeds[c] and -- through
+ *     dsg_set_step_grid -- renorm_host[c] renorm steps;
+ *   - dsg_sample and dsg_sample_rec fail (they are not chunked calls), and so does a chunked call with a renorm hook installed.
+ * The arrays are copied into device buffers the handle owns.  Like the other settings calls this one takes no stream: it selects the
+ * handle's device itself and synchronises that device before it overwrites the buffers (an enqueued call may still read them); removing
+ * the setting overwrites nothing and does not synchronise.  The step graphs of the variant form are cached beside the plain ones and do
+ * not depend on the values or on the buffers: a new set replaces contents only. */
+int dsg_set_chunk_variants(dsg_handle* h, const float* omega_host, const int* renorm_host, const int* table_host, int chunks, int tables);
+
 /* One training step's forward + backward: loss = DDPM.forward(y, cond) (classifier_free_MSR.py:100-112) and
  * d(loss)/d(theta) for every denoiser tensor, as `loss.backward()` produces them (classifier_free_MSR.py:223-224).
  *   y [B][D], cond [B][C] row-major;  ts [B] int32 in [0,T);  noise [B][D];  cond_mask [B] (0/1) -- the three random
