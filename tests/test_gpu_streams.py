@@ -17,7 +17,7 @@ One protocol for every case `f() -> outputs` over input buffers on the device (r
   4. both clones equal `want` bit for bit; `want` is within the bound the existing test of that entry point holds it to (CPU oracle,
      numpy restatement or bit-for-bit composition); and, unless the case is listed as synchronising, `ev.query()` is still False when
      `f` returns: "the calls do not synchronise" in the steady state.  A case listed as synchronising (with its reason, read from
-     csrc/dsg_api.hip) must have waited for the delay instead: both lists are pinned.
+     the host side under csrc/) must have waited for the delay instead: both lists are pinned.
 
 The delay is 10 x the longest enqueue time of the table, at least 20 ms, at most 250 ms, calibrated once with a pair of events.  A control
 case runs `torch.softmax` under the same protocol from the DEFAULT stream: it must see the decoys, or the whole module fails -- side
@@ -57,7 +57,8 @@ def case(cid, entries, build, *args, sync=None):
     CASES.append(Case(cid, tuple(entries), sync, build, args))
 
 
-# reasons of the synchronising cases, read from csrc/dsg_api.hip
+# reasons of the synchronising cases, read from the host side: csrc/host_forward.hpp (prepare_fused, the driver of the forward tables, and
+# run_cond_embed), csrc/host_sample.hpp (sample_impl, enqueue_step) and csrc/dsg_api.hip (the entry points)
 SYNC_F32_COND = "exact-f32 mode: run_cond_embed uploads the <= 32-wide blocks' table from a reused host vector and synchronises `stream` first"
 SYNC_CHUNK_SEEDS = "dsg_sample_chunked uploads the per-chunk seeds from pageable host memory and synchronises `stream` behind the copy"
 SYNC_PROFILE = "DSG_SAMPLE_PROFILE reads its HIP events back: one hipStreamSynchronize per step"
