@@ -147,6 +147,9 @@ class _Native:
         self.epoch = 0
         self.named_params = None
         self.storage_keys = frozenset()   # (storage pointer, device) of every parameter: what an optimizer must own to matter
+        # what DDPM's sampling calls made the handle hold, so that a repeated call sets nothing (a setter synchronises the device)
+        self.step_grid = None             # (handle, plan, its coef on the device), or None: dsg_set_step_grid
+        self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
         _NATIVES.add(self)
 
     def __deepcopy__(self, memo):
@@ -156,12 +159,7 @@ class _Native:
         return {}
 
     def __setstate__(self, state):
-        self.handle = None
-        self.bound_key = None
-        self.epoch = 0
-        self.named_params = None
-        self.storage_keys = frozenset()
-        _NATIVES.add(self)
+        self.__init__()
 
     def __del__(self):
         try:

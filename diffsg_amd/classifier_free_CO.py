@@ -10,11 +10,11 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 import torch
-import torch.optim as optim
-import torch.utils.data as data
 
+from . import entry
 from .ddpm import DDPMCore
-from .diffusion import generate_cosine_schedule, init_weights
+from .diffusion import generate_cosine_schedule
+from .entry import device as _device
 from .UNetCF import UNet1D
 
 DEFAULT_DATASET = "../datasets/3nodes_50000samples_new.csv"
@@ -84,31 +84,13 @@ def build_model(node_num, cond_dim, device, T=20, custom_config=None):
     return DDPM(T, model, node_num, alphas, device, (1, node_num), custom_config, 0.1, 0.9999, 10, 5, False)
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: this build of DiffSG has no CPU path")
-    return torch.device("cuda:0")
-
-
 def train_ddpm_co(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                   lr=0.005, milestones=(15, 80, 150), log=print):
     """classifier_free_CO.py:203-252."""
     X_train, Y_train, _, _, custom_config = co_data_load(dataset_path)
-    dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
-    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
-    device, rank, world = dp_context()      # one process per GPU when launched under torch.distributed.run; else cuda:0
-    loader = make_loader(dataset, batch_size, rank, world)
     node_num = Y_train.shape[1]
-    if device is None:
-        device = _device()                  # raises: no CPU path
-    diffusion_model = build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config)
-    diffusion_model.apply(init_weights)
-    diffusion_model.to(device)
-    sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)
-    optimizer = FlatAdam(diffusion_model, lr=lr)  # torch Adam, same update rule, over one flat tensor (one launch)
-    scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
-    run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, device, log)
-    return diffusion_model
+    return entry.train(lambda device: build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config), X_train, Y_train, lr,
+                       milestones, epochs, use_ema, warmup_epoch, batch_size, log)
 
 
 def cost_calc(X, Y):
@@ -126,21 +108,15 @@ def customized_real_decoder(Y_pred):
 @torch.no_grad()
 def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, batch_size=512, log=print, repeats=1, steps=None,
                  sampler="strided", eta=0.0, variants=None):
-    """classifier_free_CO.py:293-356.  `repeats` > 1: that many draws per test row, the one with the lowest cost scored
-    (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
-    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
-    single-setting spelling and are not read then."""
+    """classifier_free_CO.py:293-356.  `repeats`, `steps` / `sampler` / `eta` and `variants`: see `entry`; the objective is the lowest
+    cost."""
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     device = _device()
-    diffusion_model = build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config)
-    diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = entry.load_checkpoint(build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config), ckpt_path, device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
-    if variants is not None and repeats < 2:
-        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
+    entry.check_variants(variants, repeats)
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
@@ -148,13 +124,7 @@ def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, bat
         best = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants)
         Yd, pred_cost = best.solution, best.objective
     else:
-        # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
-        # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-        if batch_size % 32 == 0:
-            Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
-        else:
-            Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
-        Yd = customized_real_decoder(Y_pred)
+        Yd = customized_real_decoder(entry.sample_in_batches(diffusion_model, X, omega, batch_size, plan))
         pred_cost = cost_calc(Xt, Yd)
     true_cost = cost_calc(Xt, Yt)
     weights = 2 ** torch.arange(node_num - 1, -1, -1, device=device)
@@ -180,12 +150,10 @@ def load_test_co_debug(ckpt_path, dataset_path=DEFAULT_DATASET, T=400, omega=150
     X_train, Y_train, X_test, Y_test, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     device = _device()
-    diffusion_model = build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config)
-    diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = entry.load_checkpoint(build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config), ckpt_path, device)
     x = torch.tensor(X_test[:batch_size], dtype=torch.float32, device=device)
     diffusion_model.record_denoise_path = True
-    Y_pred = diffusion_model.sample_checked(x, omega)
+    Y_pred = diffusion_model.sample(x, omega)
     diffusion_model.record_denoise_path = False
     ys = diffusion_model.y_i_record.reshape(x.shape[0], T, -1)
     es = diffusion_model.eps_i_record.reshape(x.shape[0], T, -1)
@@ -229,21 +197,9 @@ def validate_ddpm_co(epochs=500, T=500, use_ema=False, warmup_epoch=5, batch_siz
                      milestones=(30, 150, 350), data_split=None, log=print):
     """classifier_free_CO.py:451-502: train on the validation set (uncond_prob 0.0, MultiStepLR [30,150,350])."""
     X_train, Y_train, _, _, custom_config = data_split if data_split is not None else validation_data_gen()
-    dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
-    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
-    device, rank, world = dp_context()      # one process per GPU when launched under torch.distributed.run; else cuda:0
-    loader = make_loader(dataset, batch_size, rank, world)
     node_num = Y_train.shape[1]
-    if device is None:
-        device = _device()
-    diffusion_model = _validation_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config, 0.0)
-    diffusion_model.apply(init_weights)
-    diffusion_model.to(device)
-    sync_replicas(diffusion_model)          # every replica starts from rank 0's draw (as train_ddpm_co)
-    optimizer = FlatAdam(diffusion_model, lr=lr)
-    scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
-    run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, device, log)
-    return diffusion_model
+    return entry.train(lambda device: _validation_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config, 0.0), X_train,
+                       Y_train, lr, milestones, epochs, use_ema, warmup_epoch, batch_size, log)
 
 
 @torch.no_grad()
@@ -254,18 +210,12 @@ def test_ddpm(ckpt_path=None, T=500, omega=30.0, batch_size=512, diffusion_model
     node_num = Y_train.shape[1]
     device = _device()
     if diffusion_model is None:
-        diffusion_model = _validation_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config, 0.1)
-        diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
+        diffusion_model = entry.load_checkpoint(_validation_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config, 0.1),
+                                                ckpt_path, device)
     diffusion_model.to(device)
     X = torch.tensor(X_test, dtype=torch.float32)
-    # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
-    # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-    if batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size)
-    else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega) for i in range(0, len(X), batch_size)])
     from .decode import row_softmax
-    Y_pred = row_softmax(Y_pred)
+    Y_pred = row_softmax(entry.sample_in_batches(diffusion_model, X, omega, batch_size))
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
     weights = 2 ** torch.arange(node_num - 1, -1, -1, device=device)
     pred_cls = ((Y_pred > 0.1).long() * weights).sum(dim=1)

@@ -10,11 +10,11 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 import torch
-import torch.optim as optim
-import torch.utils.data as data
 
+from . import entry
 from .ddpm import DDPMCore
-from .diffusion import generate_cosine_schedule, init_weights
+from .diffusion import generate_cosine_schedule
+from .entry import device as _device
 from .UNetCF import UNet1D
 
 DEFAULT_DATASET = "../datasets/3c_10w_10000samples.csv"
@@ -64,31 +64,13 @@ def build_model(M, cond_dim, device, T=20, custom_config=None, W=10.0):
     return DDPM(T, model, M, W, alphas, device, (1, M), custom_config, 0.1, 0.9999, 10, 5, False)
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: this build of DiffSG has no CPU path")
-    return torch.device("cuda:0")
-
-
 def train_ddpm_msr(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                    lr=0.005, milestones=(100, 150), log=print):
     """classifier_free_MSR.py:187-236 (hot loop :217-234)."""
     X_train, Y_train, _, _, custom_config = msr_data_load(dataset_path)
-    dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
-    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
-    device, rank, world = dp_context()      # one process per GPU when launched under torch.distributed.run; else cuda:0
-    loader = make_loader(dataset, batch_size, rank, world)
     M, W = custom_config['M'], custom_config['W']
-    if device is None:
-        device = _device()                  # raises: no CPU path
-    diffusion_model = build_model(M, custom_config['sfn'] * M, device, T, custom_config, W)
-    diffusion_model.apply(init_weights)
-    diffusion_model.to(device)
-    sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)
-    optimizer = FlatAdam(diffusion_model, lr=lr)  # torch Adam, same update rule, over one flat tensor (one launch)
-    scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
-    run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, device, log)
-    return diffusion_model
+    return entry.train(lambda device: build_model(M, custom_config['sfn'] * M, device, T, custom_config, W), X_train, Y_train, lr, milestones,
+                       epochs, use_ema, warmup_epoch, batch_size, log)
 
 
 def custom_decoder(Y_pred):
@@ -100,48 +82,29 @@ def custom_decoder(Y_pred):
 @torch.no_grad()
 def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, log=print, repeats=1, steps=None,
                   sampler="strided", eta=0.0, variants=None):
-    """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats` > 1: that many draws per test
-    row, the one with the best sum rate scored (DDPM.sample_best); 1 is the reference's single draw.
-    `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
-    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
-    single-setting spelling and are not read then."""
+    """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats`, `steps` / `sampler` / `eta` and
+    `variants`: see `entry`; the objective is the sum rate."""
     _, _, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
-    diffusion_model = build_model(M, custom_config['sfn'] * M, device, T, custom_config, W)
-    diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = entry.load_checkpoint(build_model(M, custom_config['sfn'] * M, device, T, custom_config, W), ckpt_path, device)
+    from .decode import msr_rate
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
-    if variants is not None and repeats < 2:
-        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
+    entry.check_variants(variants, repeats)
     X = torch.tensor(X_test, dtype=torch.float32)
-    if repeats > 1:
-        Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
-        Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
-        from .decode import msr_rate
-        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants).objective
-        true_rate = msr_rate(Yt, Xt)
-        out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
-               "avg_rate_diff": float(torch.mean(pred_rate - true_rate)), "repeats": int(repeats)}
-        log(f"less ratio: {out['less_ratio']}")
-        log(f"avg rate diff:\n {out['avg_rate_diff']}")
-        return out
-    # each 512-row chunk is its own sample() call, as in the reference (:273-279): the early-step renorm is per call
-    # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
-    # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-    if batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
-    else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)
-    from .decode import msr_rate
-    Yd = W * custom_decoder(Y_pred)
-    pred_rate, true_rate = msr_rate(Yd, Xt), msr_rate(Yt, Xt)
+    if repeats > 1:
+        pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants).objective
+    else:
+        # each 512-row chunk is its own sample() call, as in the reference (:273-279): the early-step renorm is per call
+        pred_rate = msr_rate(W * custom_decoder(entry.sample_in_batches(diffusion_model, X, omega, batch_size, plan)), Xt)
+    true_rate = msr_rate(Yt, Xt)
     out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
            "avg_rate_diff": float(torch.mean(pred_rate - true_rate))}
+    if repeats > 1:
+        out["repeats"] = int(repeats)
     log(f"less ratio: {out['less_ratio']}")
     log(f"avg rate diff:\n {out['avg_rate_diff']}")
     return out
@@ -155,12 +118,10 @@ def load_test_msr_debug(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=150
     _, _, X_test, _, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
-    diffusion_model = build_model(M, custom_config['sfn'] * M, device, T, custom_config, W)
-    diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = entry.load_checkpoint(build_model(M, custom_config['sfn'] * M, device, T, custom_config, W), ckpt_path, device)
     X = torch.tensor(X_test, dtype=torch.float32, device=device)[list(want2look)]
     diffusion_model.record_denoise_path = True
-    Y_pred = diffusion_model.sample_checked(X, omega)
+    Y_pred = diffusion_model.sample(X, omega)
     diffusion_model.record_denoise_path = False
     ys = diffusion_model.y_i_record.reshape(X.shape[0], T, -1)
     es = diffusion_model.eps_i_record.reshape(X.shape[0], T, -1)

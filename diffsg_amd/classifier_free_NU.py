@@ -8,11 +8,11 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 import torch
-import torch.optim as optim
-import torch.utils.data as data
 
+from . import entry
 from .ddpm import DDPMCore
-from .diffusion import generate_cosine_schedule, init_weights
+from .diffusion import generate_cosine_schedule
+from .entry import device as _device
 from .UNetCF import UNet1D
 
 DEFAULT_DATASET = "../datasets/3u_18mW_10000samples.csv"
@@ -67,30 +67,12 @@ def build_model(K, P_sum, device, T=20, custom_config=None):
     return DDPM(T, model, K, P_sum, alphas, device, (1, 2 + K), custom_config, 0.1, 0.9999, 10, 5, False)
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: this build of DiffSG has no CPU path")
-    return torch.device("cuda:0")
-
-
 def train_ddpm_nu(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                   lr=0.004, milestones=(80, 200), width=400, height=400, log=print):
     """classifier_free_NU.py:213-264."""
     X_train, Y_train, _, _, _, custom_config = nu_data_load(dataset_path, width, height)
-    dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
-    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
-    device, rank, world = dp_context()      # one process per GPU when launched under torch.distributed.run; else cuda:0
-    loader = make_loader(dataset, batch_size, rank, world)
-    if device is None:
-        device = _device()                  # raises: no CPU path
-    diffusion_model = build_model(custom_config['K'], custom_config['P_sum'], device, T, custom_config)
-    diffusion_model.apply(init_weights)
-    diffusion_model.to(device)
-    sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)
-    optimizer = FlatAdam(diffusion_model, lr=lr)  # torch Adam, same update rule, over one flat tensor (one launch)
-    scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
-    run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, device, log)
-    return diffusion_model
+    return entry.train(lambda device: build_model(custom_config['K'], custom_config['P_sum'], device, T, custom_config), X_train, Y_train, lr,
+                       milestones, epochs, use_ema, warmup_epoch, batch_size, log)
 
 
 def custom_decoder(Y_pred, width, height, P_sum):
@@ -108,30 +90,16 @@ def rate_calc(Y_pred_decoded, X):
 @torch.no_grad()
 def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch_size=512, width=400, height=400,
                  log=print, repeats=1, steps=None, sampler="strided", eta=0.0, variants=None):
-    """classifier_free_NU.py:306-361.  `repeats` > 1: that many draws per test row, the one with the best rate scored
-    (DDPM.sample_best); 1 is the reference's single draw.  `steps` = K: sample on K of the T trained steps
-    (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as the reference.  `variants`: a list of (omega, plan) sampler settings cycled over the
-    `repeats` rounds (round r runs variants[r % len(variants)], DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the
-    single-setting spelling and are not read then."""
+    """classifier_free_NU.py:306-361.  `repeats`, `steps` / `sampler` / `eta` and `variants`: see `entry`; the objective is the best
+    rate."""
     _, _, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
     device = _device()
-    diffusion_model = build_model(K, P_sum, device, T, custom_config)
-    diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = entry.load_checkpoint(build_model(K, P_sum, device, T, custom_config), ckpt_path, device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
-    if variants is not None and repeats < 2:
-        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
+    entry.check_variants(variants, repeats)
     X = torch.tensor(X_test, dtype=torch.float32)
-    # the reference's loop of independent `batch_size`-row sample() calls (own noise, own early-step renorm per chunk), run as
-    # one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the serial calls
-    if repeats > 1:
-        Y_pred = None                       # sampled below, `repeats` rounds of the same calls
-    elif batch_size % 32 == 0:
-        Y_pred = diffusion_model.sample_chunked_checked(X.to(device), omega, batch_size, plan=plan)
-    else:
-        Y_pred = torch.cat([diffusion_model.sample_checked(X[i:i + batch_size].to(device), omega, plan=plan) for i in range(0, len(X), batch_size)])
     Xt = X.to(device).clone()
     Xt[:, 0::2] *= width
     Xt[:, 1::2] *= height
@@ -143,7 +111,7 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
         # width / height of THIS call, as custom_decoder below gets them (the hook reads the model's custom_config: the same values)
         pred_rate = diffusion_model.sample_best(X.to(device), Xt, repeats, omega, chunk_rows=batch_size, plan=plan, variants=variants).objective
     else:
-        pred_rate = rate_calc(custom_decoder(Y_pred, width, height, P_sum), Xt)
+        pred_rate = rate_calc(custom_decoder(entry.sample_in_batches(diffusion_model, X, omega, batch_size, plan), width, height, P_sum), Xt)
     true_rate = rate_calc(Yt, Xt)
     out = {"less_ratio": float(torch.sum(pred_rate) / torch.sum(true_rate)),
            "avg_rate_diff": float(torch.mean(pred_rate - true_rate))}

@@ -1194,21 +1194,55 @@ struct UpdateArgs {
     int record_y;             // steps without the renorm: this launch also records y (otherwise k_record after the renorm)
 };
 
-__global__ __launch_bounds__(256) void k_update(const UpdateArgs a) {
+// Chunk variants (dsg_set_chunk_variants, DESIGN.md 15): every chunk of a chunked call has its own omega, its own coefficient table out of
+// `tables` stacked ones (cp.coef is then [tables][T][4]) and its own number of early renormalised steps.  Like CallParams the block lives in
+// device memory and is written per call (k_set_var), so that the captured step graphs of the variant form depend on none of it.
+struct VarParams {
+    const float* omega;   // device [chunks]
+    const int* renorm;    // device [chunks], or null: `renorm_default` for every chunk
+    const int* table;     // device [chunks], or null: table 0 for every chunk
+    int renorm_default;   // the call's own count: min(T, 4), or dsg_set_step_grid's
+};
+__global__ void k_set_var(VarParams* dst, const VarParams vp) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = vp;
+}
+
+// The setting of one step's update: a row of the coefficient table and the guidance weight.
+struct StepSetting { float c1, c2, c3, omega, w1; bool noisy; };
+__device__ __forceinline__ StepSetting step_setting(const float* row, float omega) {
+    return StepSetting{row[0], row[1], row[2], omega, 1.0f + omega, row[3] != 0.f};
+}
+
+// The ancestral update (MSR.py:128-134), one body in two forms.  Plain (k_update): one setting for the call, read in front of the loop,
+// and the trajectory record.  VAR (k_update_var): the setting of the quad's chunk, read per quad (a chunk is a multiple of 32 rows, so a
+// quad never straddles chunks); a variants call never records the trajectory (dsg_sample_rec refuses while variants are held), so `rec`
+// and `recy` are compile-time null.  Both draw from the same Philox stream (`step`) with the chunk-local index and read the same
+// injected-noise row T-1-step -- iff the (chunk's) c4 != 0 --, so a chunk's result is the bits of its own sample() call.
+template <bool VAR>
+__device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams* __restrict__ vpp) {
     const int step = *a.step_ptr;
     const CallParams cp = *a.cp;
-    const float c1 = cp.coef[4 * step], c2 = cp.coef[4 * step + 1], c3 = cp.coef[4 * step + 2];
-    const bool noisy = cp.coef[4 * step + 3] != 0.f;
-    const float omega = cp.omega, w1 = 1.0f + cp.omega;
+    VarParams vp{};
+    StepSetting st{};
+    if constexpr (VAR) vp = *vpp;
+    else st = step_setting(cp.coef + 4 * step, cp.omega);
     const size_t n4 = (a.n + 3) / 4;
-    const float* zrow = (cp.z && noisy) ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;
-    float* rec = cp.rec_eps ? cp.rec_eps + (size_t)(cp.T - 1 - step) * a.n : nullptr;
-    float* recy = (a.record_y && cp.rec_y) ? cp.rec_y + (size_t)(cp.T - 1 - step) * a.n : nullptr;
+    // plain: null on a noise-free step.  VAR: the row base, dereferenced by noisy chunks only (rows exist for step >= 2)
+    const float* zbase = (cp.z && (VAR || st.noisy)) ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;
+    float* rec = (!VAR && cp.rec_eps) ? cp.rec_eps + (size_t)(cp.T - 1 - step) * a.n : nullptr;
+    float* recy = (!VAR && a.record_y && cp.rec_y) ? cp.rec_y + (size_t)(cp.T - 1 - step) * a.n : nullptr;
     // whole quads, 16-byte aligned everywhere: one dwordx4 per stream and thread (same arithmetic per element)
     const bool quads = (a.n & 3) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zrow) |
+                       ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zbase) |
                          reinterpret_cast<uintptr_t>(rec) | reinterpret_cast<uintptr_t>(recy)) & 15) == 0;
     for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
+        if constexpr (VAR) {
+            const size_t c = cp.chunk_n4 ? i4 / cp.chunk_n4 : 0;
+            st = step_setting(cp.coef + ((size_t)(vp.table ? vp.table[c] : 0) * cp.T + step) * 4, vp.omega[c]);
+        }
+        const float c1 = st.c1, c2 = st.c2, c3 = st.c3, omega = st.omega, w1 = st.w1;
+        const bool noisy = st.noisy;
+        const float* zrow = noisy ? zbase : nullptr;
         float zz[4] = {0.f, 0.f, 0.f, 0.f};
         if (noisy && !zrow) { unsigned long long sd; size_t li; chunk_of(cp, i4, sd, li); normal4(sd, (uint32_t)step, li, zz); }
         if (quads) {
@@ -1242,89 +1276,27 @@ __global__ __launch_bounds__(256) void k_update(const UpdateArgs a) {
         }
     }
 }
+__global__ __launch_bounds__(256) void k_update(const UpdateArgs a) { update_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void k_update_var(const UpdateArgs a, const VarParams* __restrict__ vpp) { update_body<true>(a, vpp); }
 
-// Chunk variants (dsg_set_chunk_variants, DESIGN.md 15): every chunk of a chunked call has its own omega, its own coefficient table out of
-// `tables` stacked ones (cp.coef is then [tables][T][4]) and its own number of early renormalised steps.  Like CallParams the block lives in
-// device memory and is written per call (k_set_var), so that the captured step graphs of the variant form depend on none of it.
-struct VarParams {
-    const float* omega;   // device [chunks]
-    const int* renorm;    // device [chunks], or null: `renorm_default` for every chunk
-    const int* table;     // device [chunks], or null: table 0 for every chunk
-    int renorm_default;   // the call's own count: min(T, 4), or dsg_set_step_grid's
-};
-__global__ void k_set_var(VarParams* dst, const VarParams vp) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = vp;
-}
-
-// k_update with the setting of the quad's chunk (a chunk is a multiple of 32 rows, so a quad never straddles chunks): the same
-// expressions in the same order, the same Philox stream (`step`) and chunk-local index, the same injected-noise row T-1-step -- read iff
-// THIS chunk's c4 != 0 --, the 16-byte quad path and the scalar path.  A chunk's result is the bits of its own sample() call.  A variants
-// call never records the trajectory (dsg_sample_rec refuses while variants are held), so the record stores are not here.
-__global__ __launch_bounds__(256) void k_update_var(const UpdateArgs a, const VarParams* __restrict__ vpp) {
-    const int step = *a.step_ptr;
-    const CallParams cp = *a.cp;
-    const VarParams vp = *vpp;
-    const size_t n4 = (a.n + 3) / 4;
-    const float* zbase = cp.z ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;   // dereferenced by noisy chunks only (rows exist for step >= 2)
-    const bool quads = (a.n & 3) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zbase)) & 15) == 0;
-    for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
-        const size_t c = cp.chunk_n4 ? i4 / cp.chunk_n4 : 0;
-        const float* row = cp.coef + ((size_t)(vp.table ? vp.table[c] : 0) * cp.T + step) * 4;
-        const float c1 = row[0], c2 = row[1], c3 = row[2];
-        const bool noisy = row[3] != 0.f;
-        const float omega = vp.omega[c], w1 = 1.0f + omega;
-        const float* zrow = noisy ? zbase : nullptr;
-        float zz[4] = {0.f, 0.f, 0.f, 0.f};
-        if (noisy && !zrow) { unsigned long long sd; size_t li; chunk_of(cp, i4, sd, li); normal4(sd, (uint32_t)step, li, zz); }
-        if (quads) {
-            const float4 e0 = ld4(a.eps + i4 * 4), e1 = ld4(a.eps + a.n + i4 * 4), yv = ld4(a.y + i4 * 4);
-            if (zrow) { const float4 zv = ld4(zrow + i4 * 4); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
-            const float e0a[4] = {e0.x, e0.y, e0.z, e0.w}, e1a[4] = {e1.x, e1.y, e1.z, e1.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
-            float out[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const float e = __fsub_rn(__fmul_rn(w1, e1a[p]), __fmul_rn(omega, e0a[p]));
-                const float v = __fmul_rn(__fsub_rn(ya[p], __fmul_rn(c1, e)), c2);
-                out[p] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
-            }
-            st4(a.y + i4 * 4, make_float4(out[0], out[1], out[2], out[3]));
-            continue;
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const size_t i = i4 * 4 + p;
-            if (i < a.n) {
-                if (zrow) zz[p] = zrow[i];
-                const float e = __fsub_rn(__fmul_rn(w1, a.eps[a.n + i]), __fmul_rn(omega, a.eps[i]));
-                const float v = __fmul_rn(__fsub_rn(a.y[i], __fmul_rn(c1, e)), c2);
-                a.y[i] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
-            }
-        }
-    }
-}
-
-// y_T ~ N(0, 1) on device (throughput mode; the reference draws it on the host, MSR.py:115)
-__global__ void k_randn(float* __restrict__ y, size_t n, unsigned long long seed, unsigned stream) {
+// y_T ~ N(0, 1) on device (throughput mode; the reference draws it on the host, MSR.py:115).  CHUNKED, the start state of a chunked call:
+// chunk c = k_randn(seeds[c]) on its own elements
+template <bool CHUNKED>
+__device__ __forceinline__ void randn_body(float* __restrict__ y, size_t n, unsigned long long seed, const unsigned long long* __restrict__ seeds,
+                                           size_t chunk_n4, unsigned stream) {
     const size_t n4 = (n + 3) / 4;
     for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
+        size_t li = i4;
+        if constexpr (CHUNKED) { const size_t c = i4 / chunk_n4; seed = seeds[c]; li = i4 - c * chunk_n4; }
         float zz[4];
-        normal4(seed, stream, i4, zz);
+        normal4(seed, stream, li, zz);
         for (int p = 0; p < 4; ++p)
             if (i4 * 4 + p < n) y[i4 * 4 + p] = zz[p];
     }
 }
-
-// start state of a chunked call: chunk c = k_randn(seed[c]) on its own elements
+__global__ void k_randn(float* __restrict__ y, size_t n, unsigned long long seed, unsigned stream) { randn_body<false>(y, n, seed, nullptr, 0, stream); }
 __global__ void k_randn_chunked(float* __restrict__ y, size_t n, const unsigned long long* __restrict__ seeds, size_t chunk_n4, unsigned stream) {
-    const size_t n4 = (n + 3) / 4;
-    for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
-        const size_t c = i4 / chunk_n4;
-        float zz[4];
-        normal4(seeds[c], stream, i4 - c * chunk_n4, zz);
-        for (int p = 0; p < 4; ++p)
-            if (i4 * 4 + p < n) y[i4 * 4 + p] = zz[p];
-    }
+    randn_body<true>(y, n, 0ull, seeds, chunk_n4, stream);
 }
 
 // device-side trajectory ring (replaces the reference's per-step .cpu().numpy(), MSR.py:139-141); no-op when disabled
@@ -1410,12 +1382,21 @@ __global__ __launch_bounds__(256) void k_renorm_apply_stats(float* __restrict__ 
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         y[i] = (y[i] - mean) / sd;
 }
-// ... and, fused, the trajectory record of the renormalised y (k_record's job on these steps): `cp` / `step_ptr` null = no record
-__global__ __launch_bounds__(256) void k_renorm_apply(float* y, size_t n, const double* __restrict__ part,
-                                                      const double* __restrict__ part2, size_t chunk_n = 0,
-                                                      const CallParams* __restrict__ cp = nullptr, const int* __restrict__ step_ptr = nullptr) {
+// The standardisation from k_renorm_sum's partials, one body in two forms.  Plain (k_renorm_apply): fused with it the trajectory record of
+// the renormalised y (k_record's job on these steps): `cp` / `step_ptr` null = no record.  VAR (k_renorm_apply_var, chunk variants): behind
+// a predicate on the chunk and without the record.  Chunk c = blockIdx.y standardises on the first renorm[c] steps of the call, the device
+// step indices i > T-1-renorm[c]; on the other steps its elements are not touched (its sums were formed and are dropped).  Same grid,
+// strides and order in both forms: the bits of the chunk's own call.
+template <bool VAR>
+__device__ __forceinline__ void renorm_apply_body(float* y, size_t n, const double* __restrict__ part, const double* __restrict__ part2, size_t chunk_n,
+                                                  const CallParams* __restrict__ cp, const int* __restrict__ step_ptr, const VarParams* __restrict__ vp) {
     float* rec = nullptr;
-    if (cp && cp->rec_y) rec = cp->rec_y + (size_t)(cp->T - 1 - *step_ptr) * n + (chunk_n ? (size_t)blockIdx.y * chunk_n : 0);
+    if constexpr (VAR) {
+        const int count = vp->renorm ? vp->renorm[blockIdx.y] : vp->renorm_default;
+        if (!(*step_ptr > cp->T - 1 - count)) return;       // uniform over the block
+    } else {
+        if (cp && cp->rec_y) rec = cp->rec_y + (size_t)(cp->T - 1 - *step_ptr) * n + (chunk_n ? (size_t)blockIdx.y * chunk_n : 0);
+    }
     { const float* yc = y; renorm_chunk(yc, n, chunk_n); y = const_cast<float*>(yc); }
     part += (size_t)blockIdx.y * kRedBlocks; part2 += (size_t)blockIdx.y * kRedBlocks;
     double tot = 0.0, tot2 = 0.0;
@@ -1438,30 +1419,15 @@ __global__ __launch_bounds__(256) void k_renorm_apply(float* y, size_t n, const 
         if (rec) rec[i] = o;
     }
 }
-
-// Chunk variants: k_renorm_apply behind a predicate on the chunk.  Chunk c = blockIdx.y standardises on the first renorm[c] steps of the call,
-// the device step indices i > T-1-renorm[c], from the statistics k_renorm_sum left for it (same grid, strides and order as k_renorm_apply:
-// the bits of the chunk's own call); on the other steps its elements are not touched (its sums were formed and are dropped).
+__global__ __launch_bounds__(256) void k_renorm_apply(float* y, size_t n, const double* __restrict__ part,
+                                                      const double* __restrict__ part2, size_t chunk_n = 0,
+                                                      const CallParams* __restrict__ cp = nullptr, const int* __restrict__ step_ptr = nullptr) {
+    renorm_apply_body<false>(y, n, part, part2, chunk_n, cp, step_ptr, nullptr);
+}
 __global__ __launch_bounds__(256) void k_renorm_apply_var(float* y, size_t n, const double* __restrict__ part, const double* __restrict__ part2,
                                                           size_t chunk_n, const CallParams* __restrict__ cp, const int* __restrict__ step_ptr,
                                                           const VarParams* __restrict__ vp) {
-    const int count = vp->renorm ? vp->renorm[blockIdx.y] : vp->renorm_default;
-    if (!(*step_ptr > cp->T - 1 - count)) return;       // uniform over the block
-    { const float* yc = y; renorm_chunk(yc, n, chunk_n); y = const_cast<float*>(yc); }
-    part += (size_t)blockIdx.y * kRedBlocks; part2 += (size_t)blockIdx.y * kRedBlocks;
-    double tot = 0.0, tot2 = 0.0;
-    for (int i = 0; i < kRedBlocks; ++i) { tot += part[i]; tot2 += part2[i]; }
-    const double mean_d = tot / (double)n;
-    const float mean = (float)mean_d;
-    const double var = (tot2 - tot * mean_d) / (double)(n - 1);
-    const float sd = sqrtf((float)(var > 0.0 ? var : 0.0));
-    const size_t n4 = (reinterpret_cast<uintptr_t>(y) & 15) ? 0 : n / 4;
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x, st = (size_t)gridDim.x * blockDim.x;
-    for (size_t i4 = t; i4 < n4; i4 += st) {
-        const float4 v = ld4(y + 4 * i4);
-        st4(y + 4 * i4, make_float4((v.x - mean) / sd, (v.y - mean) / sd, (v.z - mean) / sd, (v.w - mean) / sd));
-    }
-    for (size_t i = 4 * n4 + t; i < n; i += st) y[i] = (y[i] - mean) / sd;
+    renorm_apply_body<true>(y, n, part, part2, chunk_n, cp, step_ptr, vp);
 }
 
 // EMA (ema.py:11-12): avg = decay*avg + (1-decay)*p over one flat range

@@ -4,11 +4,15 @@
 
 namespace {
 
-// use_hook: take the renorm hook's host callback on this step.  Never while capturing: the callback enqueues a real collective
-// (a rank whose graphs are already cached would not issue it: the all-reduces would pair up wrongly or hang) and the caller's
-// `renorm_stats` pointer would be baked into the cached graph and outlive the hook.
-int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, bool renorm, hipStream_t s,
-                        const Event* ev = nullptr, bool use_hook = true, int chunks = 1, size_t chunk_n = 0, bool var = false) {
+// The form of a call's steps, built once by sample_impl: one call or `chunks` independent ones of `chunk_n` elements (0: one call), with
+// per-chunk settings (`var`, chunk variants) or without, and the renorm partial sums -- one call: the handle's two partial rows; chunked:
+// [chunks][kRedBlocks] twice, one grid row per chunk.
+struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; };
+
+// ev: DSG_SAMPLE_PROFILE's event pairs, or null.  use_hook: take the renorm hook's host callback on this step.  Never while capturing:
+// the callback enqueues a real collective (a rank whose graphs are already cached would not issue it: the all-reduces would pair up
+// wrongly or hang) and the caller's `renorm_stats` pointer would be baked into the cached graph and outlive the hook.
+int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, const StepForm& f, bool renorm, hipStream_t s, const Event* ev, bool use_hook) {
     if (ev) {
         // DSG_SAMPLE_PROFILE: one event pair per operator.  A launch that covers several operators (the fused narrow run, a pair) is
         // booked on its first operator, the others read ~0.  f32_pairs = false preserves what this loop did before it shared the walk
@@ -23,15 +27,11 @@ int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, bool renor
     const unsigned ublocks = (unsigned)(((u.n + 3) / 4 + 255) / 256 < 2048 ? ((u.n + 3) / 4 + 255) / 256 : 2048);
     UpdateArgs ua = u;
     ua.record_y = renorm ? 0 : 1;
-    if (var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
+    if (f.var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
     else hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(256), 0, s, ua);
-    // the renorm partial sums.  One call: the handle's two partial rows; chunked: [chunks][kRedBlocks] twice, one grid row per chunk
-    double* const p1 = chunks > 1 ? h->red_chunks : h->red;
-    double* const p2 = chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks;
-    const size_t cn = chunks > 1 ? chunk_n : (size_t)0;
-    if (renorm && var) {   // chunk variants (never with a hook): every chunk's sums, then the apply of the chunks whose count covers this step
-        hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, chunks), dim3(256), 0, s, (const float*)u.y, u.n, p1, p2, cn);
-        hipLaunchKernelGGL(k_renorm_apply_var, dim3(kRedBlocks, chunks), dim3(256), 0, s, u.y, u.n, (const double*)p1, (const double*)p2, cn,
+    if (renorm && f.var) {   // chunk variants (never with a hook): every chunk's sums, then the apply of the chunks whose count covers this step
+        hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, f.chunks), dim3(256), 0, s, (const float*)u.y, u.n, f.p1, f.p2, f.chunk_n);
+        hipLaunchKernelGGL(k_renorm_apply_var, dim3(kRedBlocks, f.chunks), dim3(256), 0, s, u.y, u.n, (const double*)f.p1, (const double*)f.p2, f.chunk_n,
                            (const CallParams*)u.cp, (const int*)u.step_ptr, (const VarParams*)h->var_call);
     } else if (renorm && h->renorm_fn && use_hook) {
         // sharded call that standardises with the statistics of the WHOLE batch (MSR.py:136-137 on the concatenation of all
@@ -42,8 +42,8 @@ int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, bool renor
         hipLaunchKernelGGL(k_renorm_apply_stats, dim3(kRedBlocks), dim3(256), 0, s, u.y, u.n, h->renorm_stats);
         hipLaunchKernelGGL(k_record, dim3(ublocks), dim3(256), 0, s, u.y, u.n, u.cp, u.step_ptr);
     } else if (renorm) {   // the record is of the renormalised y (MSR.py:136-141): separate launches on these (at most 4) steps
-        hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, chunks), dim3(256), 0, s, (const float*)u.y, u.n, p1, p2, cn);
-        hipLaunchKernelGGL(k_renorm_apply, dim3(kRedBlocks, chunks), dim3(256), 0, s, u.y, u.n, (const double*)p1, (const double*)p2, cn,
+        hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, f.chunks), dim3(256), 0, s, (const float*)u.y, u.n, f.p1, f.p2, f.chunk_n);
+        hipLaunchKernelGGL(k_renorm_apply, dim3(kRedBlocks, f.chunks), dim3(256), 0, s, u.y, u.n, (const double*)f.p1, (const double*)f.p2, f.chunk_n,
                            (const CallParams*)u.cp, (const int*)u.step_ptr);      // + the trajectory record of the renormalised y
     }
     HIPCK(hipGetLastError());
@@ -136,6 +136,8 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     c.advance_step = h->step_dev;
     c.share_proj = split_ctx(h, c);
     if (prepare_fused(h, c, s)) return 1;
+    const StepForm form{chunks, chunk_n, var, chunks > 1 ? h->red_chunks : h->red,
+                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks};
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
@@ -146,10 +148,10 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         std::vector<Event> ev(2 * nops);
         for (auto& e : ev) HIPCK(hipEventCreate(e.put()));
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, k < n_renorm, s, ev.data(), true, chunks, chunk_n, var)) return 1;
+            if (enqueue_step(h, c, u, form, k < n_renorm, s, ev.data(), true)) return 1;
     } else if (flags & DSG_SAMPLE_NO_GRAPH) {
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, k < n_renorm, s, nullptr, true, chunks, chunk_n, var)) return 1;
+            if (enqueue_step(h, c, u, form, k < n_renorm, s, nullptr, true)) return 1;
     } else {
         // The step index is a device counter and everything per call sits in device memory, so a captured step depends only on
         // the workspace (rows, chunk count) -- not on T, the seed or the schedule.  Captured once per workspace: one early
@@ -169,7 +171,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             hipGraph_t g = nullptr;
             HIPCK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = 0;
-            for (int k = 0; k < run && !rc; ++k) rc = enqueue_step(h, c, u, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false, chunks, chunk_n, var);
+            for (int k = 0; k < run && !rc; ++k) rc = enqueue_step(h, c, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -180,7 +182,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         };
         for (int k = 0; k < n_renorm; ++k) {
             if (h->renorm_fn) {                           // the hook calls back into the host: these (<= 4) steps run eagerly
-                if (enqueue_step(h, c, u, true, s)) return 1;
+                if (enqueue_step(h, c, u, form, true, s, nullptr, true)) return 1;
             } else {
                 if (graph_of(0)) return 1;
                 HIPCK(hipGraphLaunch(G.exec[0], s));

@@ -9,6 +9,7 @@ problem modules subclass this core and keep their own positional signatures.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from functools import partial
 
 import numpy as np
@@ -53,6 +54,12 @@ class DDPMCore(nn.Module):
         self._draw_calls = 0
         self.y_i_record = None
         self.eps_i_record = None
+        # what the sampling calls remember on this object (what the handle holds is remembered beside it: UNetCF._Native)
+        self._coef_cache = None        # (key of the schedule buffers, their [T][4] table): _coef_table
+        self._coef_checked = []        # [(coef, version)] of the plan tables found noise free: _coef_noise_free
+        self._var_tables = None        # (coef tensors, device, their stack): _use_variants
+        self._range_unchecked = False  # a check_range=False call has enqueued and nobody has read the range flag since
+        self._keepalive = None         # the converted inputs of the last call, which only enqueued
 
     # ------------------------------------------------------------------ sampling
     def _coef_table(self):
@@ -60,7 +67,7 @@ class DDPMCore(nn.Module):
         float32 tensor ops on the registered buffers, plus the `i > 1` noise switch (MSR.py:129)."""
         key = tuple((b.data_ptr(), b._version) for b in (self.betas, self.sqrt_one_minus_alphas_cumprod, self.reciprocal_sqrt_alphas,
                                                          self.alphas_cumprod))
-        cached = getattr(self, "_coef_cache", None)
+        cached = self._coef_cache
         if cached is not None and cached[0] == key:      # a dozen tiny kernels per call otherwise: the buffers rarely change
             return cached[1]
         i = torch.arange(self.T, device=self.betas.device)
@@ -100,26 +107,33 @@ class DDPMCore(nn.Module):
         if check_range and seed is None and not (host_rng and y_T is None):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # the exact-f32 repeat must see the same Philox stream
         if check_range and host_rng and y_T is None:
-            # draw once here so that a repeat uses the same start state and noise
-            B0, D0 = cond.shape[0], self.model.cfg["input_dim"]
-            y_T = torch.randn(B0, *self.data_size).reshape(B0, D0)
-            zs = [torch.randn(B0, *self.data_size).reshape(B0, D0) for i in range(K - 1, 1, -1)]
-            noise = torch.stack(zs) if zs else torch.zeros(0, B0, D0)
+            y_T, noise = self._host_draws(cond.shape[0], K)     # once, here, so that a repeat uses the same start state and noise
             host_rng = False
-        out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan)
-        if cond.shape[0] == 0:
-            return out
+        launch = lambda: self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan)
+        return launch() if cond.shape[0] == 0 else self._range_checked(launch, "sample", check_range)
+
+    def _host_draws(self, B, K):
+        """Start state (B, D) and noise (K-2, B, D) of a K-step call, drawn with torch.randn on the host in the reference's order."""
+        D = self.model.cfg["input_dim"]
+        y_T = torch.randn(B, *self.data_size).reshape(B, D)
+        zs = [torch.randn(B, *self.data_size).reshape(B, D) for i in range(K - 1, 1, -1)]
+        return y_T, (torch.stack(zs) if zs else torch.zeros(0, B, D))
+
+    def _range_checked(self, launch, name, check_range):
+        """The output of `launch()`, which enqueues one call, under the range rule of `sample`'s `check_range`: read the range flag and,
+        if it is set, launch again on the exact-float32 kernels, then restore the caller's precision mode; unchecked, only remember that
+        the flag is still to be read."""
+        out = launch()
         if not check_range:
             self._range_unchecked = True
-            return out
-        if self.model.range_exceeded():
+        elif self.model.range_exceeded():
             import warnings
-            warnings.warn("DDPM.sample: activations exceeded the fp16 range of the split-f16 path; repeating the call with "
+            warnings.warn(f"DDPM.{name}: activations exceeded the fp16 range of the split-f16 path; repeating the call with "
                           "precision='f32'")
             prev = self.model.precision
             self.model.set_precision("f32")
             try:
-                out = self._sample_once(cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan)
+                out = launch()
             finally:
                 self.model.set_precision(prev)
         return out
@@ -127,7 +141,7 @@ class DDPMCore(nn.Module):
     def _raise_if_unchecked_call_saturated(self):
         """Sticky range flag of an earlier `check_range=False` call: raise here, at the next entry point, rather than let its
         saturated numbers pass silently (the flag is per handle and cleared by the query)."""
-        if getattr(self, "_range_unchecked", False):
+        if self._range_unchecked:
             self._range_unchecked = False
             if self.model.range_exceeded():
                 raise RuntimeError("libdiffsg_hip: an earlier sample(check_range=False) call on this model left the fp16 range of the "
@@ -146,16 +160,31 @@ class DDPMCore(nn.Module):
             raise ValueError(f"step plan: renorm_steps = {plan.renorm_steps} is outside 0 .. {K}")
         if not self._coef_noise_free(plan.coef):
             raise ValueError("step plan: steps 0 and 1 must be noise free (coef[:2, 3] == 0): the noise tensor has K - 2 rows")
-        if noise is not None:
-            want = (max(K - 2, 0), cond.shape[0], self.model.cfg["input_dim"])
-            if tuple(noise.shape) != want:
-                raise ValueError(f"noise must have shape {want} for a plan of {K} steps")
+        self._check_noise(noise, K, cond.shape[0], f" for a plan of {K} steps")
         return K
+
+    def _check_noise(self, noise, K, B, of=""):
+        """Injected noise of a K-step call over B rows is (K-2, B, D): one row per noisy step, K-1 .. 2."""
+        want = (max(K - 2, 0), B, self.model.cfg["input_dim"])
+        if noise is not None and tuple(noise.shape) != want:
+            raise ValueError(f"noise must have shape {want}{of}")
+
+    def _device_inputs(self, cond, y_T, noise, K):
+        """`cond`, the start state (B, D) and the noise (K-2, B, D) of a call as contiguous float32 tensors on `cond`'s device, and the
+        noise pointer: null (= device Philox) without noise; K <= 2 has no noisy step (MSR.py:129), so it is then never dereferenced."""
+        B, dev = cond.shape[0], cond.device
+        cond = cond.detach().to(torch.float32).contiguous()
+        if y_T is not None:
+            y_T = y_T.to(dev, torch.float32).reshape(B, self.model.cfg["input_dim"]).contiguous()
+        if noise is not None:
+            noise = noise.to(dev, torch.float32).contiguous()
+            self._check_noise(noise, K, B)
+        return cond, y_T, noise, _lib.ptr(noise if noise is not None and noise.numel() else None)
 
     def _coef_noise_free(self, coef):
         """coef[:2, 3] == 0, remembered per tensor (and version): the table may live on the device, where the answer costs a synchronise --
         once per table, not once per call or, with variants, once per chunk."""
-        seen = self.__dict__.setdefault("_coef_checked", [])
+        seen = self._coef_checked
         for c, v in seen:
             if c is coef and v == coef._version:
                 return True
@@ -170,7 +199,7 @@ class DDPMCore(nn.Module):
         handle holds is remembered beside it, so that repeated calls with one plan set nothing: setting a grid synchronises the device."""
         import ctypes
         nat = self.model._native
-        held = getattr(nat, "step_grid", None)          # (handle, plan, coef on the device)
+        held = nat.step_grid                            # (handle, plan, coef on the device)
         if held is not None and held[0] != hd:
             held = None
         if plan is None:
@@ -228,7 +257,7 @@ class DDPMCore(nn.Module):
         it, as `_use_plan` does: repeated calls with the same variants set nothing (setting them synchronises the device)."""
         import ctypes
         nat = self.model._native
-        held = getattr(nat, "chunk_variants", None)          # (handle, key)
+        held = nat.chunk_variants                            # (handle, key)
         if held is not None and held[0] != hd:
             held = None
         if chunks is None:
@@ -240,20 +269,16 @@ class DDPMCore(nn.Module):
         if _is_trained_grid(plan0, self.T):
             self._use_plan(hd, None, dev)                     # all T trained steps at t = i / T: the plan-less time table
         else:
-            grid = getattr(nat, "step_grid", None)
+            grid = nat.step_grid
             if not (grid is not None and grid[0] == hd and torch.equal(grid[1].t, plan0.t)):   # the renorm count of the grid is not read
                 self._use_plan(hd, plan0, dev)
         # the distinct coefficient tensors, stacked once
         coefs, table = [], []
         for _, p in chunks:
-            for j, c in enumerate(coefs):
-                if c is p.coef:
-                    break
-            else:
-                j = len(coefs)
+            if not any(c is p.coef for c in coefs):
                 coefs.append(p.coef)
-            table.append(j)
-        cache = getattr(self, "_var_tables", None)
+            table.append(next(j for j, c in enumerate(coefs) if c is p.coef))
+        cache = self._var_tables
         if cache is not None and cache[1] == dev and len(cache[0]) == len(coefs) and all(a is b for a, b in zip(cache[0], coefs)):
             stacked = cache[2]
         else:
@@ -273,18 +298,10 @@ class DDPMCore(nn.Module):
     def _sample_once(self, cond, omega, y_T, noise, seed, host_rng, use_graph, profile, plan=None):
         hd = self.model.native_handle()
         B, D, T = cond.shape[0], self.model.cfg["input_dim"], (self.T if plan is None else len(plan.taus))
-        cond = cond.detach().to(torch.float32).contiguous()
-        dev = cond.device
         if host_rng and y_T is None:
-            y_T = torch.randn(B, *self.data_size).reshape(B, D)
-            zs = [torch.randn(B, *self.data_size).reshape(B, D) for i in range(T - 1, 1, -1)]
-            noise = torch.stack(zs) if zs else torch.zeros(0, B, D)
-        if y_T is not None:
-            y_T = y_T.to(dev, torch.float32).reshape(B, D).contiguous()
-        if noise is not None:
-            noise = noise.to(dev, torch.float32).contiguous()
-            if tuple(noise.shape) != (max(T - 2, 0), B, D):
-                raise ValueError(f"noise must have shape ({max(T - 2, 0)}, {B}, {D})")
+            y_T, noise = self._host_draws(B, T)
+        cond, y_T, noise, zptr = self._device_inputs(cond, y_T, noise, T)
+        dev = cond.device
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         out = torch.empty(B, D, device=dev, dtype=torch.float32)
@@ -294,8 +311,6 @@ class DDPMCore(nn.Module):
         self._use_variants(hd, None, dev)  # a sample() call is no chunked call: per-chunk settings of an earlier one go
         coef = self._use_plan(hd, plan, dev)
         flags = 2 if profile else (0 if use_graph else 1)
-        # T <= 2 has no noisy step (MSR.py:129): a null pointer (= device Philox) is then never dereferenced
-        zptr = _lib.ptr(noise) if (noise is not None and noise.numel()) else _lib.ptr(None)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().dsg_sample_rec(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, seed, float(omega), _lib.ptr(coef), T,
                                                  _lib.ptr(out), B, flags, _lib.ptr(rec[0]) if rec is not None else _lib.ptr(None),
@@ -351,25 +366,15 @@ class DDPMCore(nn.Module):
             raise RuntimeError("DDPM.sample_chunked does not record the de-noising trajectory: call sample() per chunk "
                                "(record_denoise_path is set)")
         self._raise_if_unchecked_call_saturated()
-        hd = self.model.native_handle()
-        cond = cond.detach().to(torch.float32).contiguous()
-        dev = cond.device
         if seeds is None:
             seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(nch)]
         if len(seeds) != nch:
             raise ValueError(f"{nch} chunks need {nch} seeds")
-        if y_T is not None:
-            y_T = y_T.to(dev, torch.float32).reshape(B, D).contiguous()
-        if noise is not None:
-            noise = noise.to(dev, torch.float32).contiguous()
-            if tuple(noise.shape) != (max(T - 2, 0), B, D):
-                raise ValueError(f"noise must have shape ({max(T - 2, 0)}, {B}, {D})")
+        cond, y_T, noise, zptr = self._device_inputs(cond, y_T, noise, T)
+        dev = cond.device
         sd = (ctypes.c_ulonglong * nch)(*[int(x) & (2 ** 64 - 1) for x in seeds])
-        zptr = _lib.ptr(noise) if (noise is not None and noise.numel()) else _lib.ptr(None)
-        coef = None
 
         def launch():
-            nonlocal coef
             o = torch.empty(B, D, device=dev, dtype=torch.float32)
             hd = self.model.native_handle()
             if variants is None:
@@ -381,35 +386,18 @@ class DDPMCore(nn.Module):
                 _lib.check(_lib.lib().dsg_sample_chunked(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, sd, int(chunk_rows),
                                                          float(omega), _lib.ptr(coef), T, _lib.ptr(o), B, 0 if use_graph else 1,
                                                          _lib.stream_ptr()))
+            # the call only enqueues: keep its (converted) inputs alive until the next call on this object
+            self._keepalive = (cond, y_T, noise, coef, sd)
             return o
-
-        out = launch()
-        # the call only enqueues: keep its (converted) inputs alive until the next call on this object
-        self._keepalive = (cond, y_T, noise, coef, sd)
-        if not check_range:
-            self._range_unchecked = True
-            return out
-        if self.model.range_exceeded():
-            import warnings
-            warnings.warn("DDPM.sample_chunked: activations exceeded the fp16 range of the split-f16 path; repeating the call with "
-                          "precision='f32'")
-            prev = self.model.precision
-            self.model.set_precision("f32")
-            try:
-                out = launch()
-            finally:
-                self.model.set_precision(prev)
-        return out
+        return self._range_checked(launch, "sample_chunked", check_range)
 
     def sample_chunked_checked(self, cond, omega=1.0, chunk_rows=512, **kw):
         """`sample_chunked(..., check_range=True)` -- the default since round 4; kept for the callers of round 3."""
-        kw["check_range"] = True
-        return self.sample_chunked(cond, omega, chunk_rows, **kw)
+        return self.sample_chunked(cond, omega, chunk_rows, **{**kw, "check_range": True})
 
     def sample_checked(self, cond, omega=1.0, **kw):
         """`sample(..., check_range=True)` -- the default since round 4; kept for the callers of round 3."""
-        kw["check_range"] = True
-        return self.sample(cond, omega, **kw)
+        return self.sample(cond, omega, **{**kw, "check_range": True})
 
     def _decode_recorded(self, i, y):
         """Post-processing of the i-th recorded state (problem specific; overridden by the problem modules)."""
@@ -454,37 +442,27 @@ class DDPMCore(nn.Module):
             raise ValueError("sample_best: n must be at least 1")
         problem, params = self._best_of_problem()
         B = cond.shape[0]
-        one_call = chunk_rows is None or chunk_rows >= B          # a round is one sample() call (sample_chunked does the same)
-        u = B if one_call else int(chunk_rows)
-        per_round = 1 if one_call else (B + u - 1) // u
+        calls = best_calls(n, B, chunk_rows, max_rows, variants, omega, plan)
+        n_seeds = calls[-1].seeds.stop
         if seeds is None:
-            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(n * per_round)]
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(n_seeds)]
         seeds = [int(s) for s in np.asarray(seeds, dtype=object).reshape(-1)]
-        if len(seeds) != n * per_round:
-            raise ValueError(f"sample_best: {n} rounds of {per_round} call(s) need {n * per_round} seeds, got {len(seeds)}")
-        grouped = B > 0 and u % 32 == 0 and B % u == 0
-        group = max(1, int(max_rows) // B) if grouped else 1
-        kw = dict(use_graph=use_graph, check_range=check_range, plan=plan)   # every round runs the same step plan (None: all T steps)
+        if len(seeds) != n_seeds:
+            raise ValueError(f"sample_best: {n} rounds of {n_seeds // n} call(s) need {n_seeds} seeds, got {len(seeds)}")
         running = None
-        for r0 in range(0, n, group):
-            g = min(group, n - r0)
-            if variants is not None and not (grouped and g > 1):      # a group of one round: that round's own setting, its own call(s)
-                omega, kw["plan"] = variants[r0 % len(variants)]
-            sd = seeds[r0 * per_round:(r0 + g) * per_round]
-            if variants is not None and grouped and g > 1:
-                per_chunk = [variants[(r0 + k) % len(variants)] for k in range(g) for _ in range(per_round)]
-                Y = self.sample_chunked(cond.repeat(g, 1), 0.0, u, seeds=sd, use_graph=use_graph, check_range=check_range,
-                                        variants=per_chunk).view(g, B, -1)
-            elif grouped and g > 1:
-                Y = self.sample_chunked(cond.repeat(g, 1), omega, u, seeds=sd, **kw).view(g, B, -1)
-            elif one_call:
-                Y = self.sample(cond, omega, seed=sd[0], **kw)[None]
-            elif u % 32 == 0:
-                Y = self.sample_chunked(cond, omega, u, seeds=sd, **kw)[None]
-            else:                                                  # chunks off the 32-row tile: the serial calls
-                Y = torch.cat([self.sample(cond[i * u:(i + 1) * u], omega, seed=sd[i], **kw) for i in range(per_round)])[None]
-            running = best_of(problem, Y, X, out=running, round0=r0, return_objectives=return_objectives, **params)
+        for c in calls:
+            Y = self._best_call(c, cond, seeds[c.seeds], use_graph=use_graph, check_range=check_range).unflatten(0, (c.rounds, B))
+            running = best_of(problem, Y, X, out=running, round0=c.round0, return_objectives=return_objectives, **params)
         return running
+
+    def _best_call(self, c, cond, sd, **kw):
+        """The raw candidates (c.rounds * B, D) of one entry of `best_calls`, `sd` its seeds."""
+        if c.kind == "sample":
+            return self.sample(cond, c.omega, seed=sd[0], plan=c.plan, **kw)
+        if c.kind == "serial":                                     # chunks off the 32-row tile: the serial calls
+            return torch.cat([self.sample(cond[i * c.chunk:(i + 1) * c.chunk], c.omega, seed=s, plan=c.plan, **kw) for i, s in enumerate(sd)])
+        return self.sample_chunked(cond.repeat(c.rounds, 1) if c.rounds > 1 else cond, c.omega, c.chunk, seeds=sd, plan=c.plan,
+                                   variants=c.variants, **kw)
 
     @torch.no_grad()
     def refine(self, cond, y_start, k, omega=1.0, *, q_noise=None, noise=None, seed=None, **kw):
@@ -711,6 +689,34 @@ class DDPMCore(nn.Module):
             else:                                   # gloo has no AVG
                 dist.all_reduce(self._grad_bucket, op=dist.ReduceOp.SUM)
                 self._grad_bucket.div_(dist.get_world_size())
+
+
+BestCall = namedtuple("BestCall", "kind round0 rounds chunk omega plan variants seeds")
+
+
+def best_calls(n, B, chunk_rows, max_rows, variants=None, omega=1.0, plan=None):
+    """The calls of `sample_best` for `n` rounds over `B` conditions, in order.  `kind` "sample": a round that is one sample() call
+    (chunk_rows None or >= B); "chunked": one sample_chunked call of `chunk`-row chunks over `rounds` rounds (several where the rounds tile
+    into whole 32-row-aligned chunks: as many as keep the call at or below `max_rows` rows); "serial": a round of sample() calls on slices
+    off the 32-row tile.  `omega` / `plan`: the caller's, or round r's variants[r % len(variants)]; a call over several rounds has them
+    per chunk, as `variants`.  `seeds`: the call's slice of the seeds, one per call or per chunk, round-major."""
+    one_call = chunk_rows is None or chunk_rows >= B
+    u = B if one_call else int(chunk_rows)
+    per_round = 1 if one_call else (B + u - 1) // u
+    on_tile = u % 32 == 0
+    group = max(1, int(max_rows) // B) if B > 0 and on_tile and B % u == 0 else 1
+    kind = "sample" if one_call else "chunked" if on_tile else "serial"
+    calls = []
+    for r0 in range(0, n, group):
+        g = min(group, n - r0)
+        sd = slice(r0 * per_round, (r0 + g) * per_round)
+        if g > 1:
+            per_chunk = variants and [variants[(r0 + k) % len(variants)] for k in range(g) for _ in range(per_round)]
+            calls.append(BestCall("chunked", r0, g, u, 0.0 if variants else omega, None if variants else plan, per_chunk or None, sd))
+        else:
+            o, p = variants[r0 % len(variants)] if variants else (omega, plan)
+            calls.append(BestCall(kind, r0, 1, u, o, p, None, sd))
+    return calls
 
 
 def _is_trained_grid(plan, T):

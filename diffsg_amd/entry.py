@@ -1,0 +1,62 @@
+"""What the entry points of the three problem modules (classifier_free_{MSR,CO,NU}.py) and of trajectory.py share: the device, the
+checkpoint, the training set-up, the reference's evaluation loop and the refusal of sampler options.  A problem module keeps what is its
+own: the data loader, `build_model`, unscaling, the decoder and the objective, the metrics and their log lines.
+
+The sampler options of `load_test_msr`, `load_test_co` and `load_test_nu`, beyond the reference's arguments:
+  repeats   > 1: that many draws per test row, the one with the best objective scored (DDPM.sample_best); 1 is the reference's single draw.
+  steps     = K: sample on K of the T trained steps (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as
+            the reference.
+  variants  a list of (omega, plan) sampler settings cycled over the `repeats` rounds (round r runs variants[r % len(variants)],
+            DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the single-setting spelling and are not read then.
+"""
+from __future__ import annotations
+
+import torch
+
+
+def device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("no HIP device: this build of DiffSG has no CPU path")
+    return torch.device("cuda:0")
+
+
+def load_checkpoint(model, ckpt_path, device):
+    """`model` with the state dict stored at `ckpt_path`, on `device`."""
+    model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
+    return model.to(device)
+
+
+def check_variants(variants, repeats):
+    if variants is not None and repeats < 2:
+        raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
+
+
+def sample_in_batches(model, X, omega, batch_size, plan=None):
+    """The reference's loop of independent `batch_size`-row sample() calls over the rows of `X` (own noise, own early-step renorm per
+    chunk; classifier_free_MSR.py:273-279), run as one set of launches; chunk sizes that are not a multiple of the 32-row tile keep the
+    serial calls."""
+    dev = next(model.model.parameters()).device
+    if batch_size % 32 == 0:
+        return model.sample_chunked(X.to(dev), omega, batch_size, plan=plan)
+    return torch.cat([model.sample(X[i:i + batch_size].to(dev), omega, plan=plan) for i in range(0, len(X), batch_size)])
+
+
+def train(build, X_train, Y_train, lr, milestones, epochs, use_ema, warmup_epoch, batch_size, log):
+    """The training run of the three scripts (classifier_free_MSR.py:187-236, hot loop :217-234) on the model `build(device)` returns."""
+    import torch.optim as optim
+    import torch.utils.data as data
+    from .diffusion import init_weights
+    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
+    dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
+    dev, rank, world = dp_context()         # one process per GPU when launched under torch.distributed.run; else cuda:0
+    loader = make_loader(dataset, batch_size, rank, world)
+    if dev is None:
+        dev = device()                      # raises: no CPU path
+    diffusion_model = build(dev)
+    diffusion_model.apply(init_weights)
+    diffusion_model.to(dev)
+    sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)
+    optimizer = FlatAdam(diffusion_model, lr=lr)  # torch Adam, same update rule, over one flat tensor (one launch)
+    scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
+    run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, dev, log)
+    return diffusion_model

@@ -13,11 +13,11 @@ import numpy as np
 import pandas as pd
 import torch
 
+from .entry import device as _device, load_checkpoint
+
 
 def _load(diffusion_model, ckpt_path, device):
-    if ckpt_path is not None:
-        diffusion_model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
-    diffusion_model.to(device)
+    diffusion_model = load_checkpoint(diffusion_model, ckpt_path, device) if ckpt_path is not None else diffusion_model.to(device)
     diffusion_model.record_denoise_path = True
     return diffusion_model
 
@@ -33,12 +33,12 @@ def record_trajectories(diffusion_model, X_test, omega, batch_size=None, steps=N
     dev = next(diffusion_model.model.parameters()).device
     X = torch.as_tensor(np.asarray(X_test), dtype=torch.float32)
     if batch_size is None:
-        diffusion_model.sample_checked(X.to(dev), omega, plan=plan)
+        diffusion_model.sample(X.to(dev), omega, plan=plan)
         return np.asarray(diffusion_model.y_i_record)
     D = diffusion_model.model.cfg["input_dim"]
     out = np.zeros((X.shape[0], D * K), dtype=float)
     for i in range(0, X.shape[0], batch_size):
-        diffusion_model.sample_checked(X[i:i + batch_size].to(dev), omega, plan=plan)
+        diffusion_model.sample(X[i:i + batch_size].to(dev), omega, plan=plan)
         out[i:i + batch_size, :] = diffusion_model.y_i_record
     return out
 
@@ -55,7 +55,7 @@ def msr_trajectory_gen_store(ckpt_path="../ckpts/ddpm_msr_3c.pt", dataset_path="
     """sum_rate_trajectory_gen.py:25-51 (UNet1D(proj 128, dims (64,32,16,8), n_blocks 2), omega 500, whole test split)."""
     from . import classifier_free_MSR as M
     _, _, X_test, _, cfg = M.msr_data_load(dataset_path)
-    dev = M._device()
+    dev = _device()
     if diffusion_model is None:
         diffusion_model = M.build_model(cfg['M'], cfg['sfn'] * cfg['M'], dev, T, cfg, cfg['W'])
     return _store(record_trajectories(_load(diffusion_model, ckpt_path, dev), X_test, omega), out_csv, log)
@@ -68,7 +68,7 @@ def co_trajectory_gen_store(ckpt_path="../ckpts/ddpm_co.pt", dataset_path="../da
     """co_trajectory_gen.py:20-59 (512-row chunks of the test split)."""
     from . import classifier_free_CO as C
     _, Y_train, X_test, _, cfg = C.co_data_load(dataset_path)
-    dev = C._device()
+    dev = _device()
     node_num = Y_train.shape[1]
     if diffusion_model is None:
         diffusion_model = C.build_model(node_num, cfg['sfn'] * node_num, dev, T, cfg)
@@ -82,7 +82,7 @@ def nu_trajectory_gen_store(ckpt_path="../ckpts/ddpm_nu_3u.pt", dataset_path="..
     """classifier_free_NU.py:365-394 (`load_test_nu_debug`)."""
     from . import classifier_free_NU as N
     _, _, X_test, _, _, cfg = N.nu_data_load(dataset_path, width, height)
-    dev = N._device()
+    dev = _device()
     if diffusion_model is None:
         diffusion_model = N.build_model(cfg['K'], cfg['P_sum'], dev, T, cfg)
     return _store(record_trajectories(_load(diffusion_model, ckpt_path, dev), X_test, omega), out_csv, log)
