@@ -166,6 +166,7 @@ _SIGS = {
     "dsg_param_name": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int]),
     "dsg_param_numel": (ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_int]),
     "dsg_param_total": (ctypes.c_longlong, [ctypes.c_void_p]),
+    "dsg_generation": (ctypes.c_ulonglong, [ctypes.c_void_p]),
     "dsg_train_step": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int, ctypes.c_void_p]),
     "dsg_train_draws": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,

@@ -86,11 +86,16 @@ def build_model(node_num, cond_dim, device, T=20, custom_config=None):
 
 def train_ddpm_co(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                   lr=0.005, milestones=(15, 80, 150), log=print):
-    """classifier_free_CO.py:203-252."""
+    """classifier_free_CO.py:203-252.  The reference's signature; `entry.train_ddpm("co", ..., graph=True, seed=s)` is this call through
+    the captured step graph."""
+    return _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, log)
+
+
+def _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, log, graph=False, seed=None):
     X_train, Y_train, _, _, custom_config = co_data_load(dataset_path)
     node_num = Y_train.shape[1]
     return entry.train(lambda device: build_model(node_num, custom_config['sfn'] * node_num, device, T, custom_config), X_train, Y_train, lr,
-                       milestones, epochs, use_ema, warmup_epoch, batch_size, log)
+                       milestones, epochs, use_ema, warmup_epoch, batch_size, log, graph, seed)
 
 
 def cost_calc(X, Y):

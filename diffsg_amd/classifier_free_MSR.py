@@ -66,11 +66,16 @@ def build_model(M, cond_dim, device, T=20, custom_config=None, W=10.0):
 
 def train_ddpm_msr(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                    lr=0.005, milestones=(100, 150), log=print):
-    """classifier_free_MSR.py:187-236 (hot loop :217-234)."""
+    """classifier_free_MSR.py:187-236 (hot loop :217-234).  The reference's signature; `entry.train_ddpm("msr", ..., graph=True, seed=s)`
+    is this call through the captured step graph."""
+    return _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, log)
+
+
+def _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, log, graph=False, seed=None):
     X_train, Y_train, _, _, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     return entry.train(lambda device: build_model(M, custom_config['sfn'] * M, device, T, custom_config, W), X_train, Y_train, lr, milestones,
-                       epochs, use_ema, warmup_epoch, batch_size, log)
+                       epochs, use_ema, warmup_epoch, batch_size, log, graph, seed)
 
 
 def custom_decoder(Y_pred):

@@ -69,10 +69,15 @@ def build_model(K, P_sum, device, T=20, custom_config=None):
 
 def train_ddpm_nu(dataset_path=DEFAULT_DATASET, epochs=200, T=20, use_ema=False, warmup_epoch=5, batch_size=512,
                   lr=0.004, milestones=(80, 200), width=400, height=400, log=print):
-    """classifier_free_NU.py:213-264."""
+    """classifier_free_NU.py:213-264.  The reference's signature; `entry.train_ddpm("nu", ..., graph=True, seed=s)` is this call through
+    the captured step graph."""
+    return _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, width, height, log)
+
+
+def _train(dataset_path, epochs, T, use_ema, warmup_epoch, batch_size, lr, milestones, width, height, log, graph=False, seed=None):
     X_train, Y_train, _, _, _, custom_config = nu_data_load(dataset_path, width, height)
     return entry.train(lambda device: build_model(custom_config['K'], custom_config['P_sum'], device, T, custom_config), X_train, Y_train, lr,
-                       milestones, epochs, use_ema, warmup_epoch, batch_size, log)
+                       milestones, epochs, use_ema, warmup_epoch, batch_size, log, graph, seed)
 
 
 def custom_decoder(Y_pred, width, height, P_sum):

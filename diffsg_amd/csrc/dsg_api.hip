@@ -69,6 +69,7 @@ void dsg_destroy(dsg_handle* h) {
 }
 
 int dsg_param_count(const dsg_handle* h) { return h ? (int)h->params.size() : 0; }
+unsigned long long dsg_generation(const dsg_handle* h) { return h ? h->generation : 0ull; }
 const char* dsg_param_name(const dsg_handle* h, int i) {
     return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : "";
 }
@@ -145,7 +146,7 @@ int dsg_set_precision(dsg_handle* h, int mode) {
     DeviceGuard dg(h);
     if (mode != DSG_PRECISION_SPLIT_F16 && mode != DSG_PRECISION_F32_MFMA) return fail("unknown precision mode %d", mode);
     const bool split = mode == DSG_PRECISION_SPLIT_F16;
-    if (split != h->use_split) { (void)hipDeviceSynchronize(); free_graphs(h); h->use_split = split; }
+    if (split != h->use_split) { (void)hipDeviceSynchronize(); free_graphs(h); h->use_split = split; ++h->generation; }
     return 0;
 }
 
@@ -218,20 +219,23 @@ int dsg_set_option(dsg_handle* h, int option, int value) {
                 free_graphs(h);                 // the captured narrow-run launches hold the plan made under the other setting
                 h->fused_sig.valid = false;
                 h->opt_v8 = value != 0;
+                ++h->generation;
             }
             return 0;
-        case DSG_OPT_TRAIN_TIME_BESIDE: h->opt_time_beside = value != 0; return 0;
+        case DSG_OPT_TRAIN_TIME_BESIDE:
+            if ((value != 0) != h->opt_time_beside) { h->opt_time_beside = value != 0; ++h->generation; }
+            return 0;
         case DSG_OPT_PANEL_HALF:
-            if ((value != 0) != h->opt_panel_half) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_panel_half = value != 0; }
+            if ((value != 0) != h->opt_panel_half) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_panel_half = value != 0; ++h->generation; }
             return 0;
         case DSG_OPT_F32_PAIR:
-            if ((value != 0) != h->opt_f32_pair) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_f32_pair = value != 0; }
+            if ((value != 0) != h->opt_f32_pair) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_f32_pair = value != 0; ++h->generation; }
             return 0;
         case DSG_OPT_TILE_STEP:
-            if ((value != 0) != h->opt_tile) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_tile = value != 0; }
+            if ((value != 0) != h->opt_tile) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_tile = value != 0; ++h->generation; }
             return 0;
         case DSG_OPT_WGRAD_NARROW_PART:
-            if ((value != 0) != h->opt_wg_narrow_part) { (void)hipDeviceSynchronize(); h->opt_wg_narrow_part = value != 0; h->td_valid = false; }
+            if ((value != 0) != h->opt_wg_narrow_part) { (void)hipDeviceSynchronize(); h->opt_wg_narrow_part = value != 0; h->td_valid = false; ++h->generation; }
             return 0;
         default: return fail("dsg_set_option: unknown option %d", option);
     }
@@ -271,6 +275,7 @@ int dsg_set_launch_policy(dsg_handle* h, int coop_max_tiles, int narrow_small_ma
         free_graphs(h);                 // the captured step graphs hold the kernel forms chosen at capture time
         h->coop_max_tiles = c; h->narrow_small_max_tiles = n;
         h->panel_min_tiles = c == 0 ? 0 : kPanelMinTilesDefault;
+        ++h->generation;
     }
     return 0;
 }
@@ -354,6 +359,9 @@ int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, 
     const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
     hipStream_t s = (hipStream_t)stream;
+    // every refusal of train_step_impl comes FIRST: a refused call enqueues nothing, so *call_dev stays where it was (the tables built here
+    // are the ones train_step_impl then finds current)
+    if (train_shape_refused(h) || build_train_descs(h, B, T, s)) return 1;
     hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, s, h->tr.ts, h->tr.noise, h->tr.mask, B, D, T, keep_prob, seed, 0u,
                        (const unsigned long long*)call_dev);
     hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(64), 0, s, call_dev);

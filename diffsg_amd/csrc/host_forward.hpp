@@ -17,6 +17,7 @@ int fused_tables_current(dsg_handle* h, const RunCtx& c, bool sp, bool& current)
         const void* key[4] = {h->fw.ws, h->tr.ws, h->fw.cembed, h->fw.tb};
         if (h->fusedh_train_dev && h->fusedh_train_rows == c.nrows && !memcmp(key, h->fusedh_train_key, sizeof key)) return 0;
         if (!h->fusedh_train_dev) HIPCK(h->fusedh_train_dev.alloc(h->ops.size() + 1));
+        ++h->generation;      // the training table of the narrow run is rewritten in place for this batch size (dsg_generation)
         memcpy(h->fusedh_train_key, key, sizeof key);
         h->fusedh_train_rows = c.nrows;
     } else {

@@ -158,6 +158,12 @@ struct dsg_handle {
     std::vector<const float*> bound_ptrs;   // the caller's tensors (not owned)
     bool bound = false;
 
+    // dsg_generation: moves whenever something a captured training step (train.StepGraph) may hold stops being valid -- a workspace is
+    // freed (free_workspace, free_train_workspace), the launch plan changes (precision mode, launch policy, an option that takes another
+    // value), or the per-batch-size tables of the training step are rewritten for another batch (build_train_descs, the narrow run's
+    // training table).  Host only; never reset.
+    unsigned long long generation = 0;
+
     // fp16-split path (dsg_split.hpp): wide blocks of the sampling loop
     bool use_split = true;
     // launch policy (dsg_set_launch_policy): launches of at most this many row tiles take the small-launch kernel forms
@@ -455,6 +461,7 @@ void free_graphs(dsg_handle* h) {
 constexpr int kMaxGmax = 256;   // distinct gradient tensors whose max|G| is tracked (3 per block + 1 per Linear)
 
 void free_train_workspace(dsg_handle* h) {
+    ++h->generation;          // a captured training step holds these buffers
     h->tr = {};
     h->wg_units = h->cs_units = 0;
     h->tr_rows = h->tr_T = 0;
@@ -462,6 +469,7 @@ void free_train_workspace(dsg_handle* h) {
 }
 
 void free_workspace(dsg_handle* h) {
+    ++h->generation;
     h->fused_sig.valid = false;
     free_graphs(h);
     free_train_workspace(h);  // its descriptors point into the forward workspace

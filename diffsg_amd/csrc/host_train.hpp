@@ -387,6 +387,7 @@ int build_train_descs(dsg_handle* h, int B, int T, hipStream_t s) {
     TrainDescCollector col{h, B, T, t};
     for (const Op& op : h->ops) col.collect_op(op);
     if (col.check()) return 1;
+    ++h->generation;          // the tables below are rewritten in place (another batch size, T or mode): a captured step would read the new ones
     order_wgrad_units(h, t);
     build_fused_bwd_table(h, tiles, t.fb);
     h->fbwd_n = (int)t.fb.size();
@@ -432,15 +433,20 @@ int ensure_train_draws(dsg_handle* h) {
     return 0;
 }
 
-int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
-                    const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, hipStream_t s) {
-    // every shape the backward kernels cannot take is refused HERE, before anything is enqueued (ADVICE r5: the same check in the middle of
-    // the enqueue left forked streams unjoined and the gradient bucket half written)
+// the shapes the backward kernels cannot take (the message is set)
+int train_shape_refused(dsg_handle* h) {
     if (h->use_split)
         for (const ResP& r : h->res)
             if (r.N >= 64 && (r.in0 != r.N || (r.in1 != 0 && r.in1 != r.N)))
                 return fail("dsg_train_step: no backward kernel for a %d-wide block with inputs %d + %d wide", r.N, r.in0, r.in1);
-    if (build_train_descs(h, B, T, s)) return 1;
+    return 0;
+}
+
+int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
+                    const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, hipStream_t s) {
+    // every shape the backward kernels cannot take is refused HERE, before anything is enqueued (ADVICE r5: the same check in the middle of
+    // the enqueue left forked streams unjoined and the gradient bucket half written)
+    if (train_shape_refused(h) || build_train_descs(h, B, T, s)) return 1;
     const int D = h->d.input_dim, C = h->d.cond_dim, CG = groups_of(C), DG = groups_of(D), tiles = cdiv(B, 32);
     const int td = h->td, half = h->d.proj_dim / 2;
     const float* A = h->arena;

@@ -608,8 +608,18 @@ class DDPMCore(nn.Module):
         y32 = y.detach().to(torch.float32).contiguous()
         c32 = cond.detach().to(dev, torch.float32).contiguous()
         L = _lib.lib()
-        work = self._grad_buffers(L, hd, dev)
         call = self._draw_calls
+        dyn = getattr(self, "_call_dev", None)      # train.StepGraph: the call number lives in device memory (a captured launch would repeat it)
+        if dyn is not None:
+            # what the library cannot check on this path (it would have to read *call_dev): the by-value path's range guard, on the host
+            # mirror, and the mirror itself -- a split batch draws with a by-value call number and would leave *call_dev behind
+            if call >> 30:
+                raise RuntimeError("DDPM.forward: the call counter of the device-side draws is out of range (2^30)")
+            if self._splits(B):
+                raise RuntimeError(f"DDPM.forward: a batch of {B} rows runs as two halves with a call number passed by value "
+                                   "(DDPM.train_split_min_rows), which would leave the device-side call counter of the live train.StepGraph "
+                                   "behind its host mirror: close() the StepGraph first, or keep such batches out of its sequence")
+        work = self._grad_buffers(L, hd, dev)
         self._draw_calls += 1
         # data parallel: every rank must draw DIFFERENT ts / noise / mask for its rows (dp_context only de-correlates torch's
         # generator): the rank is folded into the Philox key, rank 0 keeps the plain seed
@@ -634,9 +644,11 @@ class DDPMCore(nn.Module):
                                             _lib.ptr(mk[lo:hi]), sa, sb, self.T, _lib.ptr(wk), _lib.ptr(ls), hi - lo, _lib.stream_ptr()))
             loss = self._run_halves(launch, hd, B, dev, work, (y32, c32, ts32, nz, mk))
         else:
-            dyn = getattr(self, "_call_dev", None)      # train.StepGraph: the call number lives in device memory (a captured launch would repeat it)
+            twin = getattr(self, "_step_twin", 0)       # train.StepGraph.step_on: this step runs on a further handle of the module
 
             def launch(handle, lo, hi, wk, ls):
+                if twin:
+                    handle = self.model.native_handle(twin=twin)
                 if dyn is not None:
                     _lib.check(L.dsg_train_step_seeded_dyn(handle, _lib.ptr(y32[lo:hi]), _lib.ptr(c32[lo:hi]), seed, _lib.ptr(dyn),
                                                            float(1.0 - self.uncond_prob), sa, sb, self.T, _lib.ptr(wk), _lib.ptr(ls), hi - lo,

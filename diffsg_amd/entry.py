@@ -41,15 +41,39 @@ def sample_in_batches(model, X, omega, batch_size, plan=None):
     return torch.cat([model.sample(X[i:i + batch_size].to(dev), omega, plan=plan) for i in range(0, len(X), batch_size)])
 
 
-def train(build, X_train, Y_train, lr, milestones, epochs, use_ema, warmup_epoch, batch_size, log):
-    """The training run of the three scripts (classifier_free_MSR.py:187-236, hot loop :217-234) on the model `build(device)` returns."""
+def train_ddpm(problem, *args, graph=False, seed=None, **kw):
+    """`train_ddpm_msr` / `train_ddpm_co` / `train_ddpm_nu` (`problem` = "msr", "co", "nu") with their own arguments and defaults, plus the
+    two options of `train`: `graph=True` trains from device-resident batches through the captured step graph, `seed` seeds its shuffling
+    and device-side draws.  The three functions keep the reference's signatures (tests/test_entry_cpu.py pins them), so the options live
+    here; `graph=False` is the function's own call."""
+    import importlib
+    import inspect
+    if problem not in ("msr", "co", "nu"):
+        raise ValueError(f"train_ddpm: problem must be 'msr', 'co' or 'nu', not {problem!r}")
+    mod = importlib.import_module(f".classifier_free_{problem.upper()}", __package__)
+    bound = inspect.signature(getattr(mod, f"train_ddpm_{problem}")).bind(*args, **kw)
+    bound.apply_defaults()
+    return mod._train(*bound.arguments.values(), graph=graph, seed=seed)
+
+
+def train(build, X_train, Y_train, lr, milestones, epochs, use_ema, warmup_epoch, batch_size, log, graph=False, seed=None):
+    """The training run of the three scripts (classifier_free_MSR.py:187-236, hot loop :217-234) on the model `build(device)` returns.
+
+    `graph=True` (opt-in; `train.run_epochs(graph=True)`): the training set lives on the device (`train.DeviceBatches`, shuffled per epoch
+    from `seed`), ts / noise / mask are drawn on the device (`device_draws = seed`, default 0 -- not torch's generator) and every step is a
+    replay of the captured step graph; the epoch loss is read, and the step health checked, once per epoch.  Data-parallel runs keep the
+    eager loop and say so."""
     import torch.optim as optim
     import torch.utils.data as data
     from .diffusion import init_weights
-    from .train import FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
+    from .train import DeviceBatches, FlatAdam, dp_context, make_loader, run_epochs, sync_replicas
     dataset = data.TensorDataset(torch.tensor(X_train, dtype=torch.float32), torch.tensor(Y_train, dtype=torch.float32))
     dev, rank, world = dp_context()         # one process per GPU when launched under torch.distributed.run; else cuda:0
-    loader = make_loader(dataset, batch_size, rank, world)
+    if graph and world > 1:
+        if rank == 0:
+            log(f"graph=True: {world} processes train data parallel, which keeps the eager loop (one all-reduce per step)")
+        graph = False
+    loader = None if graph else make_loader(dataset, batch_size, rank, world)
     if dev is None:
         dev = device()                      # raises: no CPU path
     diffusion_model = build(dev)
@@ -58,5 +82,10 @@ def train(build, X_train, Y_train, lr, milestones, epochs, use_ema, warmup_epoch
     sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)
     optimizer = FlatAdam(diffusion_model, lr=lr)  # torch Adam, same update rule, over one flat tensor (one launch)
     scheduler = optim.lr_scheduler.MultiStepLR(optimizer, list(milestones))
+    if graph:
+        diffusion_model.device_draws = 0 if seed is None else int(seed)
+        batches = DeviceBatches(*dataset.tensors, batch_size, diffusion_model.device_draws, dev)
+        run_epochs(diffusion_model, None, optimizer, scheduler, epochs, use_ema, warmup_epoch, dev, log, graph=True, batches=batches)
+        return diffusion_model
     run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, warmup_epoch, dev, log)
     return diffusion_model

@@ -129,6 +129,19 @@ int dsg_set_option(dsg_handle* h, int option, int value);
 /* Pre-size the workspace for up to `max_rows` batch rows and `max_entries` time-table rows. */
 int dsg_reserve(dsg_handle* h, int max_rows, int max_entries);
 
+/* A counter that moves whenever something a CAPTURED training step (a graph captured around dsg_train_step_seeded_dyn: train.StepGraph) may
+ * hold stops being valid; a query like dsg_param_count, no stream, host only.  It moves when
+ *   - a workspace is freed: the forward or the training workspace grows (more rows, more time-table entries, another T; dsg_reserve
+ *     included) -- the captured launches hold addresses inside them;
+ *   - the launch plan changes: dsg_set_precision, dsg_set_launch_policy, and dsg_set_option when the option takes ANOTHER value (setting
+ *     what is already held moves nothing);
+ *   - the per-batch-size tables of the training step are rewritten in place: a training step of another batch size, T or precision mode on
+ *     this handle (the captured launches would read the other step's tables).
+ * dsg_set_step_grid, dsg_set_chunk_variants, dsg_set_renorm_hook, dsg_bind_weights and sampling calls that fit the workspace do not touch
+ * the training step and do not move it.  A holder of a captured step records the value after the capture and, when it has moved, runs
+ * the step eagerly (which re-creates what is missing) and captures again.  Never decreases; 0 for a null handle. */
+unsigned long long dsg_generation(const dsg_handle* h);
+
 /* eps[B][D] = UNet1D.forward(x[B][D], t[B], cond[B][C], cond_mask[B])   (UNetCF.py:318-356).
  * t holds the already-divided time value per row, as the reference passes it (classifier_free_MSR.py:109,126). */
 int dsg_unet_forward(dsg_handle* h, const float* x, const float* t, const float* cond, const float* cond_mask,
@@ -251,7 +264,10 @@ int dsg_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, l
  * are read from DEVICE memory and moved on by the call itself:
  *   dsg_train_step_seeded_dyn  = dsg_train_step_seeded with call = *call_dev, then *call_dev += 1
  *   dsg_adam_step_dyn          = *step_dev += 1, then dsg_adam_step with lr = *lr_dev and step = *step_dev (the count after the update)
- * Same kernels on the same operands: the results are those of the by-value calls bit for bit. */
+ * Same kernels on the same operands: the results are those of the by-value calls bit for bit.  A shape dsg_train_step refuses is refused
+ * by dsg_train_step_seeded_dyn before anything is enqueued: *call_dev is then what it was.  The by-value call refuses call >= 2^30 (word 2
+ * of the Philox counter is 4 * call + kind); the library cannot read *call_dev without a synchronise, so the holder of the counter checks
+ * its host mirror (DDPM._draw_calls: DDPM.forward and train.StepGraph raise at 2^30). */
 int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, unsigned long long seed, unsigned long long* call_dev,
                               float keep_prob, const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out,
                               int B, void* stream);
