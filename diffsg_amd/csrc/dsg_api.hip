@@ -228,6 +228,9 @@ int dsg_set_option(dsg_handle* h, int option, int value) {
         case DSG_OPT_PANEL_HALF:
             if ((value != 0) != h->opt_panel_half) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_panel_half = value != 0; ++h->generation; }
             return 0;
+        case DSG_OPT_CFG_SHARE:
+            if ((value != 0) != h->opt_cfg_share) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_cfg_share = value != 0; ++h->generation; }
+            return 0;
         case DSG_OPT_F32_PAIR:
             if ((value != 0) != h->opt_f32_pair) { (void)hipDeviceSynchronize(); free_graphs(h); h->opt_f32_pair = value != 0; ++h->generation; }
             return 0;

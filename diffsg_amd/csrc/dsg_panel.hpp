@@ -42,6 +42,11 @@ constexpr int panel_lds_u4(int steps) { return 2 * panel_u4(steps) + panel_pw(st
 #ifndef DSG_STAMP_DBG
 #define DSG_STAMP_DBG 0
 #endif
+// which launches are stamped: 0 = the up block k_panel128_h<true, 0, 1, 4> (tools/panel_stamps.py); 1 = down.0 in either form,
+// k_panel128_h<false, 0, 1, 4> or k_panel128_duo_h<4> (tools/duo_stamps.py)
+#ifndef DSG_STAMP_DOWN0
+#define DSG_STAMP_DOWN0 0
+#endif
 #ifdef DSG_CYCLE_STAMPS
 constexpr int kPanelStampU4 = kPW * 128 / 2;
 #define DSG_PSTAMP(tag)                                                                                               \
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
 #ifdef DSG_CYCLE_STAMPS
     unsigned long long* const stamp_lds = reinterpret_cast<unsigned long long*>(lds + panel_lds_u4(STEPS));
     int stamp_k = 0;
-    constexpr bool STAMPED = SCLIN && EPI == 0 && STEPS == 4;
+    constexpr bool STAMPED = (DSG_STAMP_DOWN0 ? !SCLIN : SCLIN) && EPI == 0 && STEPS == 4;
 #endif
     float* const vec = reinterpret_cast<float*>(lds + 2 * PU4 + PW * kPrivSlots * kPrivU4);
     float* const g1v = vec, * const b1v = vec + kLnLdsW1, * const v2 = vec + 2 * kLnLdsW1;
@@ -777,6 +782,310 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
                         }
                 }
             }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stream's last requests are redundant: nothing may land in LDS after the end
+#ifdef DSG_CYCLE_STAMPS
+    if (STAMPED && blockIdx.x == 0) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int k = lane; k < 128; k += 64) dsg_stamp_buf[wave * 128 + k] = k < stamp_k ? stamp_lds[wave * 128 + k] : 0ull;
+        if (threadIdx.x == 0) {
+            dsg_stamp_buf[kPW * 128 + 0] = clk_t0; dsg_stamp_buf[kPW * 128 + 1] = clk_r0;
+            dsg_stamp_buf[kPW * 128 + 2] = __builtin_readcyclecounter(); dsg_stamp_buf[kPW * 128 + 3] = __builtin_amdgcn_s_memrealtime();
+            dsg_stamp_n = kPW * 128 + 4;
+        }
+    }
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------
+// BOTH classifier-free-guidance passes of a row tile in one wave (DSG_OPT_CFG_SHARE).  For the 128-wide down block
+// without a Linear shortcut and without a consuming Linear whose input is the SHARED feature_proj (Seg::wrap == tiles_per_pass: both
+// passes read the same tile), in a launch of exactly two passes, the first unconditional: the ResidualBlock adds the condition
+// embedding only behind lin2, so the LN1 statistics, norm1 -> SiLU -> lin1 (+ time bias) and norm2 -> SiLU -> lin2 (+ c2) of the
+// unconditional tile `ptile` and of the conditional tile `tiles_per_pass + ptile` are the same bits.  k_panel128_h<false, 0, 1>
+// computes them once per TILE; here a wave owns a ROW tile:
+//     stage 1, stage 2                              -> acc2                        (once)
+//     stage 3 from acc2, + c3, + x, statistics      -> store tile ptile            (unconditional)
+//     acc2 += cond_emb
+//     stage 3 from acc2, + c3, + x, statistics      -> store tile tiles_per_pass + ptile
+// Stage 3 only READS acc2 (its accumulators alias acc1), so nothing new is live; the residual input is read twice from the private
+// stream rather than held.  Every piece (panel_pipe_s, panel_prep, acc_unscale_add_lds, acc_stats) is the one k_panel128_h runs, in
+// the same order per output tile: the result is bit-identical.
+// Weight-panel program per row tile: P panels of W1, P of W2, P of W3, P of W3 again (P = 8 / STEPS), then the next group's W1.
+// Private stream per row tile: [statistics | 8 x (stage 1) | 8 x (residual) | 8 cond_emb | 8 x (residual) | next group's statistics
+// and first three x items]: 33 items where the two tiles took 42.
+template <int STEPS = 4>
+__global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(const BlockArgsH ah, const int ngroups) {
+    constexpr int N = 128, NT = 4, NG = 16;
+    constexpr int PW = panel_pw(STEPS), PU4 = panel_u4(STEPS), NTHR = 64 * PW;
+    constexpr int P = 8 / STEPS;                               // panels per stage (8 k16-steps each)
+    constexpr int PA = P, PB = 2 * P, PD = 3 * P, NP = 4 * P;  // W2 / W3 / W3 again start here; panels per row tile
+    __shared__ uint4 lds[panel_lds_u4(STEPS) + (STEPS == 4 ? kPanelStampU4 : 0)];
+#ifdef DSG_CYCLE_STAMPS
+    unsigned long long* const stamp_lds = reinterpret_cast<unsigned long long*>(lds + panel_lds_u4(STEPS));
+    int stamp_k = 0;
+    constexpr bool STAMPED = DSG_STAMP_DOWN0 && STEPS == 4;
+    const unsigned long long clk_t0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    float* const vec = reinterpret_cast<float*>(lds + 2 * PU4 + PW * kPrivSlots * kPrivU4);
+    float* const g1v = vec, * const b1v = vec + kLnLdsW1, * const v2 = vec + 2 * kLnLdsW1;
+    float* const g2v = v2, * const b2v = v2 + 128, * const g3v = v2 + 256, * const b3v = v2 + 384, * const tbv = v2 + 512, * const c2v = v2 + 640,
+         * const c3v = v2 + 768;
+    const BlockArgs& a = ah.b;
+    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int stride = gridDim.x;
+    const int tpp = a.tiles_per_pass;
+    if (STEPS == 4 && wave >= 4) __builtin_amdgcn_s_setprio(DSG_PANEL_TRAIL_PRIO);      // as k_panel128_h: the younger wave of a SIMD
+    constexpr float kL2 = -1.44269504088896341f;
+
+    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e)
+    {
+        const int n1 = ln1_extent(a);
+        for (int i = threadIdx.x; i < n1; i += NTHR) { g1v[i] = a.gamma1[i] * kL2; b1v[i] = a.beta1[i] * kL2; }
+        if (threadIdx.x < 128) {
+            const int i = threadIdx.x;
+            g2v[i] = a.gamma2[i] * kL2; b2v[i] = a.beta2[i] * kL2; g3v[i] = a.gamma3[i] * kL2; b3v[i] = a.beta3[i] * kL2;
+            c2v[i] = a.c2[i]; c3v[i] = a.c3[i];
+            tbv[i] = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + i];
+        }
+    }
+    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
+    __syncthreads();                   // no DMA is in flight yet: a plain barrier
+
+    // ---- this wave's 4 KiB of every weight panel: (out tile, two of its STEPS k16-steps)
+    const int wnt = wave / (STEPS / 2), wsub = wave % (STEPS / 2);
+    const uint4* const w1p = ah.W1h + ((size_t)wnt * 8) * 128 + wsub * 256;
+    const uint4* const w2p = ah.W2h + ((size_t)wnt * 8) * 128 + wsub * 256;
+    const uint4* const w3p = ah.W3h + ((size_t)wnt * 8) * 128 + wsub * 256;
+    // panel p of the row-tile program (compile-time p at every call site)
+    auto panel_src = [&](int p) -> const uint4* {
+        if (p < PA) return w1p + (size_t)p * (128 * STEPS);
+        if (p < PB) return w2p + (size_t)(p - PA) * (128 * STEPS);
+        if (p < PD) return w3p + (size_t)(p - PB) * (128 * STEPS);
+        return w3p + (size_t)(p - PD) * (128 * STEPS);
+    };
+    // this wave's row tile of group g: the shared input (in0 wraps at tiles_per_pass: one tile for both passes), its statistics, the
+    // condition embedding.  Waves past the last row tile walk the last one again (and store nothing).
+    struct RowPtrs { const char *x0, *st0, *cp; };
+    auto row_ptrs = [&](int g) -> RowPtrs {
+        const int raw = g * PW + wave, pt = raw < tpp ? raw : tpp - 1;
+        return RowPtrs{reinterpret_cast<const char*>(a.in0.data + (size_t)pt * 16 * 256), reinterpret_cast<const char*>(a.in0.stats + (size_t)pt * 64),
+                       reinterpret_cast<const char*>(a.cond_pre + (size_t)pt * 16 * 256)};
+    };
+
+    const unsigned lds0 = (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void*)lds;
+    PanelCtx c;
+    c.lane16 = (unsigned)lane * 16u; c.lane4 = (unsigned)lane * 4u;
+    c.w_lds = lds0 + (unsigned)wave * 4096u;
+    c.w_rd = lds0 + (unsigned)lane * 16u;
+    c.p_lds = lds0 + 2u * PU4 * 16u + (unsigned)wave * (kPrivSlots * 2048u);
+    c.wrd = lds + lane;
+    c.prd = lds + 2 * PU4 + wave * (kPrivSlots * kPrivU4) + lane;
+    c.q = 0; c.islot = 0; c.cslot = 0;
+
+    // prologue: the first four private items of this wave's first row tile, then panel 0 into buffer 0
+    {
+        const RowPtrs cur = row_ptrs(blockIdx.x < ngroups ? blockIdx.x : 0);
+        priv_issue_stats(c, cur.st0, cur.st0);
+        priv_issue(c, cur.x0);
+        priv_issue(c, cur.x0 + 2048);
+        priv_issue(c, cur.x0 + 4096);
+    }
+    glds_quad_s(c.lane16, panel_src(0), c.w_lds);
+
+    // One barrier per panel, as k_panel128_h.  `since_w`: DMA operations of the private stream issued BEHIND the pending panel's own
+    // four; 0 at the start (the prologue's requests went out IN FRONT of panel 0, so the launch's first panel is waited for with vmcnt(0)).
+    int since_w = 0;
+    auto panel_begin = [&](int next) -> int {
+        if (since_w >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+        else if (STEPS < 4 && since_w >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+        else if (since_w >= 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const int rd = c.q & 1;
+        glds_quad_s(c.lane16, panel_src(next), c.w_lds + (unsigned)((c.q + 1) & 1) * (PU4 * 16u));
+        since_w = 0;
+        ++c.q;
+        return rd;
+    };
+
+    for (int g = blockIdx.x; g < ngroups; g += stride) {
+        const int row_raw = g * PW + wave;
+        const bool live = row_raw < tpp;                // idle waves of the last group still move their pieces and meet the barriers
+        const int ptile = live ? row_raw : tpp - 1;
+        const RowPtrs cur = row_ptrs(g);
+        const RowPtrs nxt = row_ptrs(g + stride < ngroups ? g + stride : g);
+        DSG_PSTAMP(0x01);
+        // the item at position T of the part of the stream that follows stage 1 (T is a compile-time constant at every call site)
+        auto issue_at = [&](int T) {
+            if (T < 8) priv_issue(c, cur.x0 + (size_t)T * 2048);                        // residual read, unconditional pass
+            else if (T < 16) priv_issue(c, cur.cp + (size_t)(T - 8) * 2048);            // condition embedding
+            else if (T < 24) priv_issue(c, cur.x0 + (size_t)(T - 16) * 2048);           // residual read, conditional pass
+            else if (T == 24) priv_issue_stats(c, nxt.st0, nxt.st0);
+            else priv_issue(c, nxt.x0 + (size_t)(T - 25) * 2048);
+            since_w += 2;
+        };
+        // stage 1, step S: wait for its item, request the one four places ahead
+        auto consume_s1 = [&](int S) -> const uint4* {
+            const uint4* rd = priv_consume(c);
+            if (S + 4 < 8) { priv_issue(c, cur.x0 + (size_t)(S + 4) * 2048); since_w += 2; }
+            else issue_at(S + 4 - 8);
+            return rd;
+        };
+        auto no_consume = [&](int) -> const uint4* { return nullptr; };
+        auto none_n = [&]() -> const uint4* { return nullptr; };
+        auto step0_mem = [&](const uint4* rd, const float* gv, const float* bv, float cc, float dd) -> BOp {
+            const float4 xa = __builtin_bit_cast(float4, rd[0]), xb = __builtin_bit_cast(float4, rd[64]);
+            const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
+        };
+        auto step0_reg = [&](const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd) -> BOp {
+            const float x[8] = {in[0][0], in[0][1], in[0][2], in[0][3], in[0][4], in[0][5], in[0][6], in[0][7]};
+            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
+        };
+
+        // ---- stage 1 (memory-fed), once for both passes
+        f32x16 acc1[NT];
+        {
+            float cc, dd;
+            {
+                const uint4* rd = priv_consume(c);             // LN1 statistics of the one input tensor
+                const float2 s0 = reinterpret_cast<const float2*>(rd - lane)[j];
+                priv_issue(c, cur.x0 + 3 * 2048); since_w += 2;
+                const float rstd = rsqrtf(s0.y * a.inv_nin + kLnEps);
+                cc = rstd; dd = -s0.x * rstd;
+            }
+            DSG_PSTAMP(0x10);
+            BOp b0 = step0_mem(consume_s1(0), g1v, b1v, cc, dd);
+            asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
+            DSG_PSTAMP(0x11);
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const int bi = panel_begin(p + 1);
+                DSG_PSTAMP(0x14);
+                BOp bc;
+                const NextPrep nx{&acc1, STEPS * (p + 1), g1v, b1v, cc, dd, nullptr, nullptr};
+                auto cs = [&](int jj) { return consume_s1(STEPS * p + 1 + jj); };
+                auto cn = [&]() { return consume_s1(STEPS * p + STEPS); };
+                if (p + 1 < P) {
+                    if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
+                    else panel_pipe_s<false, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
+                    b0 = bc;
+                } else {
+                    panel_pipe_s<false, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
+                }
+                DSG_PSTAMP(0x12);
+            }
+        }
+        acc_unscale_add_lds<NT>(acc1, inv1, tbv, h);
+        DSG_PSTAMP(0x13);
+
+        // ---- stage 2 (register-fed), once for both passes
+        f32x16 acc2[NT];
+        {
+            float mean, m2;
+            acc_stats<N, NT>(acc1, h, mean, m2);
+            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
+            DSG_PSTAMP(0x20);
+            BOp b0 = step0_reg(acc1, g2v, b2v, cc, dd), bc;
+            asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
+            DSG_PSTAMP(0x21);
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const int bi = panel_begin(PA + p + 1);
+                DSG_PSTAMP(0x24);
+                const NextPrep nx{&acc1, STEPS * (p + 1 < P ? p + 1 : 0), g2v, b2v, cc, dd, nullptr, nullptr};
+                if (p + 1 < P) {
+                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
+                    else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
+                    b0 = bc;
+                } else {
+                    panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
+                }
+                DSG_PSTAMP(0x22);
+            }
+            acc_unscale_add_lds<NT>(acc2, inv2, c2v, h);
+        }
+        DSG_PSTAMP(0x23);
+
+        // ---- per pass: (+ condition embedding,) stage 3 from acc2, residual add, statistics, store
+        f32x16 (&acc3)[NT] = acc1;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int pbase = pass == 0 ? PB : PD;       // this pass's W3 panels
+            const int tbase = pass == 0 ? 0 : 16;        // stream position of this pass's residual items
+            if (pass == 1) {           // condition embedding of the row tile: 8 private items, one accumulator tile per two
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int i = 2 * e + hf;
+                        const uint4* rd = priv_consume(c);
+                        const float4 cv0 = __builtin_bit_cast(float4, rd[0]), cv1 = __builtin_bit_cast(float4, rd[64]);
+                        issue_at(8 + i + 4);
+                        const int r0 = 8 * hf;
+                        acc2[e][r0 + 0] += cv0.x; acc2[e][r0 + 1] += cv0.y; acc2[e][r0 + 2] += cv0.z; acc2[e][r0 + 3] += cv0.w;
+                        acc2[e][r0 + 4] += cv1.x; acc2[e][r0 + 5] += cv1.y; acc2[e][r0 + 6] += cv1.z; acc2[e][r0 + 7] += cv1.w;
+                    }
+                }
+                DSG_PSTAMP(0x33);
+            }
+            {
+                float mean, m2;
+                acc_stats<N, NT>(acc2, h, mean, m2);
+                const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
+                DSG_PSTAMP(0x30);
+                BOp b0 = step0_reg(acc2, g3v, b3v, cc, dd), bc, bsc;
+                asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
+                DSG_PSTAMP(0x31);
+                int bi = 0;
+#pragma unroll
+                for (int p = 0; p + 1 < P; ++p) {        // every panel of the stage but its last
+                    bi = panel_begin(pbase + p + 1);
+                    DSG_PSTAMP(0x34);
+                    const NextPrep nx{&acc2, STEPS * (p + 1), g3v, b3v, cc, dd, nullptr, nullptr};
+                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
+                    else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
+                    b0 = bc;
+                    DSG_PSTAMP(0x32);
+                }
+                bc = b0;                                 // operand of the stage's last panel
+                constexpr int SL = 8 - STEPS;            // its first k16-step
+                bi = panel_begin((pbase + P) % NP);      // behind the second pass: the next group's first W1 panel
+                DSG_PSTAMP(0x34);
+                panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc3, c.wrd + bi * PU4, bc, bsc, acc2, SL, g3v, b3v, cc, dd, h, no_consume,
+                                                                NextPrep{&acc2, 0, g3v, b3v, cc, dd, nullptr, nullptr}, none_n);
+                DSG_PSTAMP(0x32);
+                acc_unscale_add_lds<NT>(acc3, inv3, c3v, h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int i = 2 * e + hf;
+                        const uint4* rd = priv_consume(c);
+                        const float4 xv0 = __builtin_bit_cast(float4, rd[0]), xv1 = __builtin_bit_cast(float4, rd[64]);
+                        issue_at(tbase + i + 4);
+                        const int r0 = 8 * hf;
+                        acc3[e][r0 + 0] += xv0.x; acc3[e][r0 + 1] += xv0.y; acc3[e][r0 + 2] += xv0.z; acc3[e][r0 + 3] += xv0.w;
+                        acc3[e][r0 + 4] += xv1.x; acc3[e][r0 + 5] += xv1.y; acc3[e][r0 + 6] += xv1.z; acc3[e][r0 + 7] += xv1.w;
+                    }
+                }
+            }
+            DSG_PSTAMP(0x43);
+            // ---- statistics + store: tile `ptile` of the unconditional pass, `tiles_per_pass + ptile` of the conditional one
+            float xmean, xm2;
+            acc_stats<N, NT>(acc3, h, xmean, xm2);
+            if (live) {
+                const int tile = pass == 0 ? ptile : tpp + ptile;
+                if (h == 0) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + j] = make_float2(xmean, xm2);
+#pragma unroll
+                for (int G = 0; G < NG; ++G)
+                    st4(a.out + ((size_t)tile * NG + G) * 256 + lane * 4,
+                        make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]));
+            }
+            DSG_PSTAMP(0x50);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stream's last requests are redundant: nothing may land in LDS after the end

@@ -213,6 +213,23 @@ void launch_panel128(const dsg_handle* h, const BlockLinArgsH& w, hipStream_t s)
     hipLaunchKernelGGL((k_panel128_h<SC, EPI, NTO>), persistent_grid(h, ngroups), dim3(kPW * 64), 0, s, w, ngroups);
 }
 
+// Both guidance passes of a row tile in one wave (k_panel128_duo_h, DSG_OPT_CFG_SHARE).  The ONE copy of the rule; the caller has
+// established panel128_ok and that no Linear is fused behind the block.  The block reads the shared feature_proj (one tile for both
+// passes), the launch is exactly two passes with the first one unconditional, and the condition embeddings are precomputed.
+bool cfg_share_ok(const dsg_handle* h, const ResP& r, const BlockArgs& b) {
+    return h->opt_cfg_share && !r.sclin && b.tiles_per_pass > 0 && b.in0.wrap == b.tiles_per_pass && b.ntiles == 2 * b.tiles_per_pass &&
+           b.uncond_tiles == b.tiles_per_pass && b.cond_pre;
+}
+void launch_panel128_duo(const dsg_handle* h, const BlockArgsH& a, hipStream_t s) {
+    if (h->opt_panel_half) {
+        const int ngroups = cdiv(a.b.tiles_per_pass, 4);
+        hipLaunchKernelGGL((k_panel128_duo_h<2>), persistent_grid(h, ngroups, 2), dim3(256), 0, s, a, ngroups);
+        return;
+    }
+    const int ngroups = cdiv(a.b.tiles_per_pass, kPW);
+    hipLaunchKernelGGL((k_panel128_duo_h<4>), persistent_grid(h, ngroups), dim3(kPW * 64), 0, s, a, ngroups);
+}
+
 // 64-wide blocks of large sampling launches: the block's planes resident in LDS (dsg_res64.hpp)
 bool res64_lds_ok(const dsg_handle* h, const ResP& r, const BlockArgs& b) {
     return r.N == 64 && b.in0.groups == 8 && (b.in1.groups == 0 || b.in1.groups == 8) && (b.in1.groups != 0) == r.sclin && b.cond_pre && !b.ts &&
@@ -263,6 +280,7 @@ void launch_res_h(const dsg_handle* h, const ResP& r, const BlockArgs& b, hipStr
         return;
     }
     if (panel128_ok(h, r, a.b)) {
+        if (cfg_share_ok(h, r, a.b)) { launch_panel128_duo(h, a, s); return; }
         if (r.sclin) launch_panel128<true, 0, 1>(h, block_only(a), s); else launch_panel128<false, 0, 1>(h, block_only(a), s);
         return;
     }

@@ -223,6 +223,7 @@ struct dsg_handle {
     std::vector<FusedOpH> tileops_host;
     bool tile_valid = false, opt_tile = true;
     bool opt_panel_half = true;       // dsg_set_option(DSG_OPT_PANEL_HALF): the 128-wide panel kernels with 16 KiB panels, two workgroups per CU
+    bool opt_cfg_share = true;        // dsg_set_option(DSG_OPT_CFG_SHARE): down.0 of a two-pass step runs lin1 / lin2 once per row tile (k_panel128_duo_h)
     DevBuf<FusedOpH> fusedh_train_dev;      // the same run for the training forward (every output stored, h1/h2 saved)
     const void* fusedh_train_key[4] = {nullptr, nullptr, nullptr, nullptr}; int fusedh_train_rows = 0;
     // inference tables (dsg_sample / dsg_unet_forward / dsg_time_op share them): what the device copy was built for

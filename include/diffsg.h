@@ -121,9 +121,15 @@ int dsg_set_launch_policy(dsg_handle* h, int coop_max_tiles, int narrow_small_ma
  *                          accumulation order per element: bit-identical results; +0.3..0.9 % at 65 536 rows, 3-11 % at 12 288 - 49 152 rows.
  *   DSG_OPT_F32_PAIR       1 (default) / 0: exact-float32 path, inference: a >= 64-wide ResidualBlock and the Linear that consumes its
  *                          output (Downsample / Upsample, UNetCF.py:230-257; `final`, UNetCF.py:356) in one launch, the Linear fed from
- *                          the block's accumulators (csrc/dsg_kernels.hpp, k_resblock_lin).  Bit-identical to the two launches. */
+ *                          the block's accumulators (csrc/dsg_kernels.hpp, k_resblock_lin).  Bit-identical to the two launches.
+ *   DSG_OPT_CFG_SHARE      1 (default) / 0: large two-pass sampling launches of a 128-wide down block that reads the shared feature_proj
+ *                          (down.0 of the reverse step) run BOTH classifier-free-guidance passes of a row tile in one wave: the LN1
+ *                          statistics, lin1 and lin2 do not depend on the condition (UNetCF.py ResidualBlock adds cond_emb behind lin2) and
+ *                          are computed once; only + cond_emb, lin3, the residual add and the store run per pass (csrc/dsg_panel.hpp,
+ *                          k_panel128_duo_h).  Same arithmetic and order per element: bit-identical results.  0: one tile per pass and
+ *                          wave (k_panel128_h).  Cached step graphs are dropped when the value changes. */
 enum { DSG_OPT_NARROW_VALU8 = 1, DSG_OPT_TRAIN_TIME_BESIDE = 2, DSG_OPT_WGRAD_NARROW_PART = 4, DSG_OPT_TILE_STEP = 8, DSG_OPT_PANEL_HALF = 16,
-       DSG_OPT_F32_PAIR = 32 };
+       DSG_OPT_F32_PAIR = 32, DSG_OPT_CFG_SHARE = 64 };
 int dsg_set_option(dsg_handle* h, int option, int value);
 
 /* Pre-size the workspace for up to `max_rows` batch rows and `max_entries` time-table rows. */
