@@ -150,6 +150,7 @@ class _Native:
         # what DDPM's sampling calls made the handle hold, so that a repeated call sets nothing (a setter synchronises the device)
         self.step_grid = None             # (handle, plan, its coef on the device), or None: dsg_set_step_grid
         self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
+        self.step_guidance = None         # (handle, the weights as a tuple of floats, their tensor, its version), or None: dsg_set_step_guidance
         _NATIVES.add(self)
 
     def __deepcopy__(self, memo):

@@ -122,8 +122,9 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
     if (h->v8_ncopies > 0)      // first: the LDS image below takes the section from this buffer
         hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)h->v8_ncopies), dim3(64), 0, s, (const NarrowLdsCopy*)h->v8_copies_dev,
                            reinterpret_cast<uint4*>(h->v8_image.get()));
-    if (h->nlds_image && h->nlds_ncopies > 0)
-        hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)h->nlds_ncopies), dim3(256), 0, s, (const NarrowLdsCopy*)h->nlds_copies_dev, h->nlds_image);
+    for (auto& t : h->tabs)     // both resident sets (the one-pass context's image is a copy of its own)
+        if (t.nlds_image && t.nlds_ncopies > 0)
+            hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)t.nlds_ncopies), dim3(256), 0, s, (const NarrowLdsCopy*)t.nlds_copies_dev, t.nlds_image);
     HIPCK(hipGetLastError());
     h->bound = true;
     return 0;
@@ -178,6 +179,29 @@ int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_step
     return 0;
 }
 
+int dsg_set_step_guidance(dsg_handle* h, const float* g_host, int n) {
+    if (!h) return fail("null handle");
+    if (n < 0) return fail("dsg_set_step_guidance: n = %d is negative", n);
+    if (!g_host || n == 0) { h->guid_n = 0; return 0; }     // nothing is overwritten: an enqueued call keeps reading the buffer
+    for (int j = 0; j < n; ++j)
+        if (!(g_host[j] >= 0.f && g_host[j] <= 3.402823466e38f))     // NaN fails the first comparison, +inf the second
+            return fail("dsg_set_step_guidance: weight %d is %g: the weights are finite and >= 0", j, (double)g_host[j]);
+    DeviceGuard dg(h);
+    // an enqueued call may still read the old weights; the step graphs hold neither the buffer nor the values and stay
+    HIPCK(hipDeviceSynchronize());
+    if (!h->guid_call) HIPCK(h->guid_call.alloc(1));
+    if (n > h->guid_cap) {      // the new buffer first: a failed allocation leaves the schedule the handle holds as it was
+        DevBuf<float> grown;
+        HIPCK(grown.alloc((size_t)n));
+        h->guid_dev = std::move(grown);
+        h->guid_cap = n;
+    }
+    HIPCK(hipMemcpy(h->guid_dev, g_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    h->guid_host.assign(g_host, g_host + n);
+    h->guid_n = n;
+    return 0;
+}
+
 int dsg_set_chunk_variants(dsg_handle* h, const float* omega_host, const int* renorm_host, const int* table_host, int chunks, int tables) {
     if (!h) return fail("null handle");
     if (chunks < 0) return fail("dsg_set_chunk_variants: chunks = %d is negative", chunks);
@@ -217,7 +241,7 @@ int dsg_set_option(dsg_handle* h, int option, int value) {
             if ((value != 0) != h->opt_v8) {
                 (void)hipDeviceSynchronize();
                 free_graphs(h);                 // the captured narrow-run launches hold the plan made under the other setting
-                h->fused_sig.valid = false;
+                for (auto& t : h->tabs) t.fused_sig.valid = false;
                 h->opt_v8 = value != 0;
                 ++h->generation;
             }

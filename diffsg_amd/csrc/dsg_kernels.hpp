@@ -1206,6 +1206,10 @@ struct VarParams {
 __global__ void k_set_var(VarParams* dst, const VarParams vp) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = vp;
 }
+// dsg_set_step_guidance: the address of the weights [T], written per call like the blocks above
+__global__ void k_set_guidance(const float** dst, const float* g) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = g;
+}
 
 // The setting of one step's update: a row of the coefficient table and the guidance weight.
 struct StepSetting { float c1, c2, c3, omega, w1; bool noisy; };
@@ -1218,14 +1222,20 @@ __device__ __forceinline__ StepSetting step_setting(const float* row, float omeg
 // quad never straddles chunks); a variants call never records the trajectory (dsg_sample_rec refuses while variants are held), so `rec`
 // and `recy` are compile-time null.  Both draw from the same Philox stream (`step`) with the chunk-local index and read the same
 // injected-noise row T-1-step -- iff the (chunk's) c4 != 0 --, so a chunk's result is the bits of its own sample() call.
-template <bool VAR>
-__device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams* __restrict__ vpp) {
+// SCHED (k_update_sched, k_update_var_sched; dsg_set_step_guidance): the step's weight g = guidance[step], read once in front
+// of the loop, scales omega -- omega_j = __fmul_rn(omega, g), so g = 1 gives the bits of the unscheduled form.  g == 0 is an unguided
+// step: the denoiser ran ONE pass, which wrote eps1 to plane 0 of `eps`; only that plane is read and it is taken as eps unchanged.
+template <bool VAR, bool SCHED = false>
+__device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams* __restrict__ vpp, const float* const* __restrict__ gpp = nullptr) {
     const int step = *a.step_ptr;
     const CallParams cp = *a.cp;
     VarParams vp{};
     StepSetting st{};
+    float g = 1.0f;
+    if constexpr (SCHED) g = (*gpp)[step];
+    const bool one_pass = SCHED && g == 0.f;
     if constexpr (VAR) vp = *vpp;
-    else st = step_setting(cp.coef + 4 * step, cp.omega);
+    else st = step_setting(cp.coef + 4 * step, SCHED ? __fmul_rn(cp.omega, g) : cp.omega);
     const size_t n4 = (a.n + 3) / 4;
     // plain: null on a noise-free step.  VAR: the row base, dereferenced by noisy chunks only (rows exist for step >= 2)
     const float* zbase = (cp.z && (VAR || st.noisy)) ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;
@@ -1238,7 +1248,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
     for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
         if constexpr (VAR) {
             const size_t c = cp.chunk_n4 ? i4 / cp.chunk_n4 : 0;
-            st = step_setting(cp.coef + ((size_t)(vp.table ? vp.table[c] : 0) * cp.T + step) * 4, vp.omega[c]);
+            st = step_setting(cp.coef + ((size_t)(vp.table ? vp.table[c] : 0) * cp.T + step) * 4, SCHED ? __fmul_rn(vp.omega[c], g) : vp.omega[c]);
         }
         const float c1 = st.c1, c2 = st.c2, c3 = st.c3, omega = st.omega, w1 = st.w1;
         const bool noisy = st.noisy;
@@ -1246,13 +1256,13 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
         float zz[4] = {0.f, 0.f, 0.f, 0.f};
         if (noisy && !zrow) { unsigned long long sd; size_t li; chunk_of(cp, i4, sd, li); normal4(sd, (uint32_t)step, li, zz); }
         if (quads) {
-            const float4 e0 = ld4(a.eps + i4 * 4), e1 = ld4(a.eps + a.n + i4 * 4), yv = ld4(a.y + i4 * 4);
+            const float4 e0 = ld4(a.eps + i4 * 4), e1 = one_pass ? e0 : ld4(a.eps + a.n + i4 * 4), yv = ld4(a.y + i4 * 4);
             if (zrow) { const float4 zv = ld4(zrow + i4 * 4); zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w; }
             const float e0a[4] = {e0.x, e0.y, e0.z, e0.w}, e1a[4] = {e1.x, e1.y, e1.z, e1.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
             float ea[4], out[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                ea[p] = __fsub_rn(__fmul_rn(w1, e1a[p]), __fmul_rn(omega, e0a[p]));
+                ea[p] = one_pass ? e0a[p] : __fsub_rn(__fmul_rn(w1, e1a[p]), __fmul_rn(omega, e0a[p]));
                 const float v = __fmul_rn(__fsub_rn(ya[p], __fmul_rn(c1, ea[p])), c2);
                 out[p] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
             }
@@ -1266,7 +1276,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
             const size_t i = i4 * 4 + p;
             if (i < a.n) {
                 if (zrow) zz[p] = zrow[i];
-                const float e = __fsub_rn(__fmul_rn(w1, a.eps[a.n + i]), __fmul_rn(omega, a.eps[i]));
+                const float e = one_pass ? a.eps[i] : __fsub_rn(__fmul_rn(w1, a.eps[a.n + i]), __fmul_rn(omega, a.eps[i]));
                 if (rec) rec[i] = e;
                 const float v = __fmul_rn(__fsub_rn(a.y[i], __fmul_rn(c1, e)), c2);
                 const float o = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
@@ -1278,6 +1288,10 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
 }
 __global__ __launch_bounds__(256) void k_update(const UpdateArgs a) { update_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256) void k_update_var(const UpdateArgs a, const VarParams* __restrict__ vpp) { update_body<true>(a, vpp); }
+__global__ __launch_bounds__(256) void k_update_sched(const UpdateArgs a, const float* const* __restrict__ gpp) { update_body<false, true>(a, nullptr, gpp); }
+__global__ __launch_bounds__(256) void k_update_var_sched(const UpdateArgs a, const VarParams* __restrict__ vpp, const float* const* __restrict__ gpp) {
+    update_body<true, true>(a, vpp, gpp);
+}
 
 // y_T ~ N(0, 1) on device (throughput mode; the reference draws it on the host, MSR.py:115).  CHUNKED, the start state of a chunked call:
 // chunk c = k_randn(seeds[c]) on its own elements

@@ -98,6 +98,7 @@ struct RunCtx {
     bool cond_pre;       // condition embeddings precomputed for this call (dsg_sample)
     int* advance_step = nullptr;   // reverse loop: feature_proj decrements the step index (LinArgs::advance_step)
     bool share_proj = false;       // reverse loop, split path: feature_proj(y) computed for ONE pass, read by both (Seg::wrap)
+    int set = 0;                   // which resident table set (dsg_handle::tabs) the context's tables live in; 1: the one-pass context of a scheduled call
 };
 
 size_t cap_tiles_of(const dsg_handle* h) { return (size_t)cdiv(h->cap_rows, 32) * 2; }
@@ -406,7 +407,7 @@ void launch_op(const dsg_handle* h, const Op& op, const RunCtx& c, hipStream_t s
     if (narrow_singles(h, c) && fusable(h, op) && opi >= 0 && opi < (long long)h->ops.size()) {
         const int ntiles = cdiv(c.nrows, 32) * c.npass;
         const size_t at = h->ops.size() + 1 + (size_t)opi;
-        hipLaunchKernelGGL(k_fused_narrow, dim3(cdiv(ntiles, kWavesPerBlock)), dim3(256), 0, s, (const FusedOp*)(h->fused_dev + at), 1, ntiles);
+        hipLaunchKernelGGL(k_fused_narrow, dim3(cdiv(ntiles, kWavesPerBlock)), dim3(256), 0, s, (const FusedOp*)(h->tabs[c.set].fused_dev + at), 1, ntiles);
         return;
     }
     if (op.kind == OP_RES) {
@@ -445,21 +446,21 @@ int launch_fused(const dsg_handle* h, const RunCtx& c, hipStream_t s) {
     const int ntiles = cdiv(c.nrows, 32) * c.npass;
     const dim3 grid = wave_grid(ntiles), block(256);
     if (!split_ctx(h, c)) {
-        hipLaunchKernelGGL(k_fused_narrow, grid, block, 0, s, h->fused_dev, h->fuse_hi - h->fuse_lo, ntiles);
+        hipLaunchKernelGGL(k_fused_narrow, grid, block, 0, s, h->tabs[c.set].fused_dev, h->fuse_hi - h->fuse_lo, ntiles);
         return 0;
     }
-    const FusedOpH* tab = c.train ? h->fusedh_train_dev : h->fusedh_dev;
-    if (!c.train && !c.ts && h->nlds_valid && ntiles >= h->panel_min_tiles && ntiles > h->narrow_small_max_tiles) {
+    const FusedOpH* tab = c.train ? h->fusedh_train_dev : h->tabs[c.set].fusedh_dev;
+    if (!c.train && !c.ts && h->tabs[c.set].nlds_valid && ntiles >= h->panel_min_tiles && ntiles > h->narrow_small_max_tiles) {
         // large sampling launch: the run's planes and vectors resident in LDS, one launch walks the phases (dsg_split.hpp)
         NarrowPhases P;
         memset(&P, 0, sizeof P);
-        P.n = (int)h->nlds_phases.size();
-        for (int k = 0; k < P.n; ++k) P.p[k] = h->nlds_phases[k];
-        const NarrowLdsOp* lops = h->nlds_ops_dev;
+        P.n = (int)h->tabs[c.set].nlds_phases.size();
+        for (int k = 0; k < P.n; ++k) P.p[k] = h->tabs[c.set].nlds_phases[k];
+        const NarrowLdsOp* lops = h->tabs[c.set].nlds_ops_dev;
         dispatch_v8nb((h->opt_v8 && h->v8_lo >= 0) ? h->d.n_blocks : 0, [&](auto nb) {
             hipLaunchKernelGGL(k_fused_narrow_lds<DSG_V(nb)>, dim3(cdiv(ntiles, 16)), dim3(1024), 0, s, tab, lops, P, ntiles, c.step_ptr, h->tb_stride);
         });
-        return h->nlds_tail ? 1 : 0;
+        return h->tabs[c.set].nlds_tail ? 1 : 0;
     }
     // the 8-wide bottom of the net on the vector unit (float32, dsg_narrow8.hpp) from the global image: sampling launches below the
     // LDS form's threshold, dsg_unet_forward, and the training forward (which stores what the backward pass reads)
@@ -542,7 +543,7 @@ bool try_dual64(const dsg_handle* h, int i, const RunCtx& c, hipStream_t s) {
 
 // Small launches: feature_proj, then ONE launch that carries every row tile through the rest of the net (dsg_tile.hpp)
 bool tile_step_ok(const dsg_handle* h, const RunCtx& c) {
-    return h->opt_tile && h->tile_valid && split_ctx(h, c) && !c.train && !c.ts && h->fuse_hi - h->fuse_lo >= 2 &&
+    return h->opt_tile && h->tabs[c.set].tile_valid && split_ctx(h, c) && !c.train && !c.ts && h->fuse_hi - h->fuse_lo >= 2 &&
            cdiv(c.nrows, 32) * c.npass <= h->coop_max_tiles;
 }
 void launch_tile_step(const dsg_handle* h, const RunCtx& c, hipStream_t s) {
@@ -550,7 +551,7 @@ void launch_tile_step(const dsg_handle* h, const RunCtx& c, hipStream_t s) {
     const int ntiles = cdiv(c.nrows, 32) * c.npass, nops = (int)h->ops.size();
     const V8Sec v8 = v8_section(h, c);
     dispatch_v8nb(v8.nb, [&](auto nb) {
-        hipLaunchKernelGGL((k_unet_tile<DSG_V(nb)>), dim3(ntiles), dim3(256), 0, s, (const FusedOpH*)h->tileops_dev, 1, nops, ntiles, h->fuse_lo, h->fuse_hi,
+        hipLaunchKernelGGL((k_unet_tile<DSG_V(nb)>), dim3(ntiles), dim3(256), 0, s, (const FusedOpH*)h->tabs[c.set].tileops_dev, 1, nops, ntiles, h->fuse_lo, h->fuse_hi,
                            v8.at, v8.n, (const float*)h->v8_image);
     });
 }

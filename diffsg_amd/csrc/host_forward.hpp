@@ -26,11 +26,11 @@ int fused_tables_current(dsg_handle* h, const RunCtx& c, bool sp, bool& current)
         const void* ptrs[8] = {c.y, c.eps_out, c.step_ptr, c.ts, h->fw.ws, h->fw.cembed, h->fw.tb,
                                reinterpret_cast<const void*>((size_t)h->cap_rows * 2 + (c.cond_pre ? 1 : 0))};
         memcpy(sig.p, ptrs, sizeof ptrs);
-        const dsg_handle::FusedSig& o = h->fused_sig;
+        const dsg_handle::FusedSig& o = h->tabs[c.set].fused_sig;
         if (o.valid && o.sp == sig.sp && o.share == sig.share && o.nrows == sig.nrows && o.npass == sig.npass && o.uncond_tiles == sig.uncond_tiles &&
             !memcmp(o.p, sig.p, sizeof sig.p))
             return 0;
-        h->fused_sig = sig;
+        h->tabs[c.set].fused_sig = sig;
     }
     current = false;
     return 0;
@@ -39,11 +39,11 @@ int fused_tables_current(dsg_handle* h, const RunCtx& c, bool sp, bool& current)
 // exact path: every narrow operator as a chain of ONE, in the second half of fused_host (launch_op, narrow_singles)
 void build_singles_table(dsg_handle* h, const RunCtx& c) {
     const size_t nops = h->ops.size();
-    h->fused_host.assign(2 * (nops + 1), FusedOp{});
+    h->tabs[c.set].fused_host.assign(2 * (nops + 1), FusedOp{});
     for (size_t k = 0; k < nops; ++k) {
         const Op& op = h->ops[k];
         if (!fusable(h, op)) continue;
-        FusedOp& f = h->fused_host[nops + 1 + k];
+        FusedOp& f = h->tabs[c.set].fused_host[nops + 1 + k];
         memset(&f, 0, sizeof f);
         f.kind = op.kind == OP_RES ? 0 : 1;
         f.N = f.kind == 0 ? h->res[op.p].N : h->lin[op.p].l.N;
@@ -65,13 +65,13 @@ bool build_narrow_table(dsg_handle* h, const RunCtx& c, bool sp, int n) {
         const int sclin = kind == 0 ? (int)h->res[op.p].sclin : 0;
         if (kind == 0) fill_block_args(h, op, c, b); else fill_lin_args(h, op, c, l);
         if (sp) {
-            FusedOpH& f = h->fusedh_host[i];
+            FusedOpH& f = h->tabs[c.set].fusedh_host[i];
             memset(&f, 0, sizeof f);
             f.kind = kind; f.N = N; f.sclin = sclin;
             f.store_out = (c.train || h->tensors[op.out].is_skip || i == n - 1) ? 1 : 0;   // training: the backward reads every tensor
             if (kind == 0) fill_block_args_h(h, h->res[op.p], b, f.b); else fill_lin_args_h(h, h->lin[op.p], l, f.l);
         } else {
-            FusedOp& f = h->fused_host[i];
+            FusedOp& f = h->tabs[c.set].fused_host[i];
             memset(&f, 0, sizeof f);
             f.kind = kind; f.N = N; f.sclin = sclin; f.b = b; f.l = l;
             // a link of the chain (bit 1): input handed over in registers; stored (bit 0) if something else reads it from memory
@@ -88,8 +88,8 @@ bool build_narrow_table(dsg_handle* h, const RunCtx& c, bool sp, int n) {
     LinArgs l;
     memset(&l, 0, sizeof l);
     fill_lin_args(h, t, c, l);
-    h->fusedh_host.resize(n + 1);
-    FusedOpH& f = h->fusedh_host[n];
+    h->tabs[c.set].fusedh_host.resize(n + 1);
+    FusedOpH& f = h->tabs[c.set].fusedh_host[n];
     memset(&f, 0, sizeof f);
     f.kind = 2; f.N = 64; f.store_out = 1;
     fill_lin_args_h(h, h->lin[t.p], l, f.l);
@@ -100,14 +100,14 @@ bool build_narrow_table(dsg_handle* h, const RunCtx& c, bool sp, int n) {
 // memory); sets tile_valid and uploads the table when the net has the shapes the kernel covers
 int build_tile_table(dsg_handle* h, const RunCtx& c, hipStream_t s) {
     const int nops = (int)h->ops.size();
-    h->tileops_host.assign(nops, FusedOpH{});
+    h->tabs[c.set].tileops_host.assign(nops, FusedOpH{});
     bool ok = nops >= 2 && h->ops[0].kind == OP_PROJ && h->fuse_lo >= 1;
     int wide = 0;
     for (int i = 0; i < nops && ok; ++i) {
         const Op& op = h->ops[i];
-        FusedOpH& f = h->tileops_host[i];
+        FusedOpH& f = h->tabs[c.set].tileops_host[i];
         memset(&f, 0, sizeof f);
-        if (i >= h->fuse_lo && i < h->fuse_hi) { f = h->fusedh_host[i - h->fuse_lo]; continue; }
+        if (i >= h->fuse_lo && i < h->fuse_hi) { f = h->tabs[c.set].fusedh_host[i - h->fuse_lo]; continue; }
         f.store_out = 1;
         if (op.kind == OP_ATTN) { ok = false; break; }      // k_unet_tile has not learned the operator: per-operator launches
         if (op.kind == OP_RES) {
@@ -128,16 +128,17 @@ int build_tile_table(dsg_handle* h, const RunCtx& c, hipStream_t s) {
             else if (l.l.N > 128 || (op.kind == OP_FINAL) != l.lnact) ok = false;
         }
     }
-    h->tile_valid = ok && wide > 0;
-    if (h->tile_valid)
-        HIPCK(hipMemcpyAsync(h->tileops_dev, h->tileops_host.data(), (size_t)nops * sizeof(FusedOpH), hipMemcpyHostToDevice, s));
+    h->tabs[c.set].tile_valid = ok && wide > 0;
+    if (h->tabs[c.set].tile_valid)
+        HIPCK(hipMemcpyAsync(h->tabs[c.set].tileops_dev, h->tabs[c.set].tileops_host.data(), (size_t)nops * sizeof(FusedOpH), hipMemcpyHostToDevice, s));
     return 0;
 }
 
 // LDS image of the run, cut into phases that fit kNarrowLdsU4: per operator its packed planes and per-feature vectors (static:
-// gathered once into h->nlds_image, a phase's part contiguous) and, behind them, the phase's slice of the time-table row
+// gathered once into tb.nlds_image, a phase's part contiguous) and, behind them, the phase's slice of the time-table row
 struct NarrowLdsPlan {
     dsg_handle* h;
+    dsg_handle::InferTables& tb;                // the table set of the context the plan is made for
     int n, n_all;                               // operators of the run; with the tail Linear when it joined the last phase
     std::vector<NarrowLdsOp> lops;
     std::vector<NarrowLdsCopy> copies;          // dst_u4: offset in the GLOBAL image buffer
@@ -149,7 +150,7 @@ struct NarrowLdsPlan {
     int s_lo, s_hi;
     unsigned s_u4, s_tb_u4;
 
-    NarrowLdsPlan(dsg_handle* h_, int n_) : h(h_), n(n_), n_all(n_), lops(n_ + 1) {
+    NarrowLdsPlan(dsg_handle* h_, dsg_handle::InferTables& tb_, int n_) : h(h_), tb(tb_), n(n_), n_all(n_), lops(n_ + 1) {
         s_lo = (h->opt_v8 && h->v8_lo >= 0) ? h->v8_lo - h->fuse_lo : -1; s_hi = s_lo >= 0 ? h->v8_hi - h->fuse_lo : -1;
         const int s_nb = h->d.n_blocks;
         s_u4 = (unsigned)(s_nb == 3 ? V8SecL<3>::SIZE : V8SecL<2>::SIZE) / 4; s_tb_u4 = (unsigned)(2 * s_nb + 3) * 8;
@@ -177,7 +178,7 @@ struct NarrowLdsPlan {
             ph.v8_at = s_lo; ph.v8_nops = s_hi - s_lo; ph.v8_sec = 4 * lops[s_lo].w1; ph.v8_store = lops[s_lo].store_out;
             ph.v8_tb = 4 * used + (unsigned)(h->res[h->ops[h->fuse_lo + s_lo + 1].p].tb_off - tb_first);
         }
-        h->nlds_phases.push_back(ph);              // the image pointer is filled by upload() (it needs the buffer): phase_base remembers where
+        tb.nlds_phases.push_back(ph);              // the image pointer is filled by upload() (it needs the buffer): phase_base remembers where
         for (int k = phase_lo; k < hi; ++k) {      // the time-bias rows sit behind the static part
             const Op& o = h->ops[h->fuse_lo + k];
             if (o.kind == OP_RES) lops[k].tb = 4 * used + (unsigned)(h->res[o.p].tb_off - tb_first);
@@ -204,12 +205,12 @@ bool NarrowLdsPlan::place_op(int i) {
     if (used + need + tb_now() + need_tb > (unsigned)kNarrowLdsU4) {
         close_phase(i);
         // (round 6: one launch walks every phase, the running tensor crosses the boundary in registers)
-        if ((int)h->nlds_phases.size() >= kNarrowMaxPhases) return false;
+        if ((int)tb.nlds_phases.size() >= kNarrowMaxPhases) return false;
         phase_base.push_back(image_base);
         phase_lo = i; used = 0; tb_first = -1; tb_last_end = 0;
     }
     NarrowLdsOp& lo = lops[i];
-    lo.store_out = h->fusedh_host[(s_lo >= 0 && i == s_lo) ? s_hi - 1 : i].store_out;
+    lo.store_out = tb.fusedh_host[(s_lo >= 0 && i == s_lo) ? s_hi - 1 : i].store_out;
     if (i == s_lo) {
         // the section's image as one piece (gathered at bind time into h->v8_image, dsg_bind_weights)
         lo.w1 = take(h->v8_image, s_u4);
@@ -247,28 +248,28 @@ void NarrowLdsPlan::place_tail() {
 
 int NarrowLdsPlan::upload(hipStream_t s) {
     const size_t image_u4 = image_base;
-    if (!h->nlds_ops_dev) HIPCK(h->nlds_ops_dev.alloc(h->ops.size() + 1));
-    if (!h->nlds_copies_dev) HIPCK(h->nlds_copies_dev.alloc((h->ops.size() + 1) * 16));
-    if (image_u4 + 1 > h->nlds_image_cap) {
+    if (!tb.nlds_ops_dev) HIPCK(tb.nlds_ops_dev.alloc(h->ops.size() + 1));
+    if (!tb.nlds_copies_dev) HIPCK(tb.nlds_copies_dev.alloc((h->ops.size() + 1) * 16));
+    if (image_u4 + 1 > tb.nlds_image_cap) {
         // grow-only: the captured step graphs hold the image pointer (phase arguments are passed by value); when it has
         // to move, every graph captured with the old one goes (nothing is in flight: the stream was synchronised by the driver)
-        if (h->nlds_image) { h->nlds_image.reset(); free_graphs(h); }
-        HIPCK(h->nlds_image.alloc(image_u4 + 1));
-        h->nlds_image_cap = image_u4 + 1;
+        if (tb.nlds_image) { tb.nlds_image.reset(); free_graphs(h); }
+        HIPCK(tb.nlds_image.alloc(image_u4 + 1));
+        tb.nlds_image_cap = image_u4 + 1;
     }
-    HIPCK(hipMemcpy(h->nlds_ops_dev, lops.data(), n_all * sizeof(NarrowLdsOp), hipMemcpyHostToDevice));
-    h->nlds_tail = n_all > n;
-    HIPCK(hipMemcpy(h->nlds_copies_dev, copies.data(), copies.size() * sizeof(NarrowLdsCopy), hipMemcpyHostToDevice));
-    for (size_t k = 0; k < h->nlds_phases.size(); ++k) h->nlds_phases[k].image = h->nlds_image + phase_base[k];
-    hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)copies.size()), dim3(256), 0, s, (const NarrowLdsCopy*)h->nlds_copies_dev, h->nlds_image);
-    h->nlds_ncopies = (int)copies.size();
-    h->nlds_valid = true;
+    HIPCK(hipMemcpy(tb.nlds_ops_dev, lops.data(), n_all * sizeof(NarrowLdsOp), hipMemcpyHostToDevice));
+    tb.nlds_tail = n_all > n;
+    HIPCK(hipMemcpy(tb.nlds_copies_dev, copies.data(), copies.size() * sizeof(NarrowLdsCopy), hipMemcpyHostToDevice));
+    for (size_t k = 0; k < tb.nlds_phases.size(); ++k) tb.nlds_phases[k].image = tb.nlds_image + phase_base[k];
+    hipLaunchKernelGGL(k_narrow_image_build, dim3((unsigned)copies.size()), dim3(256), 0, s, (const NarrowLdsCopy*)tb.nlds_copies_dev, tb.nlds_image);
+    tb.nlds_ncopies = (int)copies.size();
+    tb.nlds_valid = true;
     return 0;
 }
 
-int build_lds_plan(dsg_handle* h, int n, bool tail, hipStream_t s) {
-    NarrowLdsPlan plan(h, n);
-    h->nlds_phases.clear();
+int build_lds_plan(dsg_handle* h, dsg_handle::InferTables& tb, int n, bool tail, hipStream_t s) {
+    NarrowLdsPlan plan(h, tb, n);
+    tb.nlds_phases.clear();
     for (int i = 0; i < n; ++i)
         if (!plan.place_op(i)) return 0;              // does not fit: nlds_valid stays false, the run takes its other forms
     if (n <= 0) return 0;
@@ -287,16 +288,16 @@ int prepare_fused(dsg_handle* h, const RunCtx& c, hipStream_t s) {
     if (fused_tables_current(h, c, sp, current)) return 1;
     if (current) return 0;
     HIPCK(hipStreamSynchronize(s));  // the host tables may still be the source of an earlier async copy
-    if (sp) h->fusedh_host.resize(n); else h->fused_host.resize(n);
+    if (sp) h->tabs[c.set].fusedh_host.resize(n); else h->tabs[c.set].fused_host.resize(n);
     if (singles) build_singles_table(h, c);
     const bool tail = build_narrow_table(h, c, sp, n);
-    if (sp) HIPCK(hipMemcpyAsync(c.train ? h->fusedh_train_dev : h->fusedh_dev, h->fusedh_host.data(), h->fusedh_host.size() * sizeof(FusedOpH), hipMemcpyHostToDevice, s));
-    else HIPCK(hipMemcpyAsync(h->fused_dev, h->fused_host.data(), (singles ? h->fused_host.size() : (size_t)n) * sizeof(FusedOp), hipMemcpyHostToDevice, s));
+    if (sp) HIPCK(hipMemcpyAsync(c.train ? h->fusedh_train_dev : h->tabs[c.set].fusedh_dev, h->tabs[c.set].fusedh_host.data(), h->tabs[c.set].fusedh_host.size() * sizeof(FusedOpH), hipMemcpyHostToDevice, s));
+    else HIPCK(hipMemcpyAsync(h->tabs[c.set].fused_dev, h->tabs[c.set].fused_host.data(), (singles ? h->tabs[c.set].fused_host.size() : (size_t)n) * sizeof(FusedOp), hipMemcpyHostToDevice, s));
     if (sp && !c.train && build_tile_table(h, c, s)) return 1;
     // the training forward has its own table and leaves the inference plan (and fused_sig) alone: resetting the LDS plan here
     // would drop the eager sampling path to the non-LDS kernels for good while cached graphs keep replaying the LDS form
-    if (!c.train) { h->nlds_valid = false; h->nlds_tail = false; }
-    if (sp && !c.train && !c.ts) return build_lds_plan(h, n, tail, s);
+    if (!c.train) { h->tabs[c.set].nlds_valid = false; h->tabs[c.set].nlds_tail = false; }
+    if (sp && !c.train && !c.ts) return build_lds_plan(h, h->tabs[c.set], n, tail, s);
     return 0;
 }
 

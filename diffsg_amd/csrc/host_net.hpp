@@ -112,11 +112,15 @@ constexpr int kWgForkMinTiles = 1024;
 // One set of captured reverse steps of a workspace shape: exec[0] = one early (renorm) step, exec[1 + k] = 2^k later steps
 // (runs of 1, 2, 4, 8, 16, 32), and the shape they were captured for
 constexpr int kStepRunGraphs = 6;
+// the kinds of a step: the plain one, and under a guidance schedule (dsg_set_step_guidance) the two-pass step with the
+// scheduled update and the one-pass (unguided) step
+enum StepKind { STEP_PLAIN = 0, STEP_SCHED = 1, STEP_ONEPASS = 2, kStepKinds = 3 };
 struct StepGraphs {
-    GraphExec exec[1 + kStepRunGraphs];
+    GraphExec exec[kStepKinds][1 + kStepRunGraphs];
     int rows = -1, chunks = -1, chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
     void reset() {
-        for (auto& g : exec) g.reset();
+        for (auto& k : exec)
+            for (auto& g : k) g.reset();
         rows = chunks = chunk_rows = -1;
     }
 };
@@ -202,6 +206,12 @@ struct dsg_handle {
     // dsg_set_step_grid: the time value of every step index of a sampling call and the number of early renormalised steps; grid_n == 0: no
     // grid (t = i / T, min(T, 4) renorm steps).  The buffer only grows and is kept when the grid is removed.
     DevBuf<float> grid_dev; int grid_n = 0, grid_cap = 0, grid_renorm = 0;
+    // dsg_set_step_guidance: one weight per step index of a sampling call; guid_n == 0: none held.  The buffer only grows and is kept when
+    // the setting is removed.  The host copy chooses the launch sequence (a zero weight: a one-pass step).  The step graphs of the scheduled
+    // kinds hold `guid_call` alone (one pointer, allocated once), never the buffer: k_set_guidance writes its address per call.
+    DevBuf<float> guid_dev; int guid_n = 0, guid_cap = 0;
+    std::vector<float> guid_host;
+    DevBuf<const float*> guid_call;
     double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device, not owned), reduced across ranks by `renorm_fn`
     void (*renorm_fn)(void*) = nullptr; void* renorm_user = nullptr;
     int device = 0;              // the device that was current in dsg_create: the settings / status entry points select it themselves
@@ -214,29 +224,40 @@ struct dsg_handle {
 
     // fused narrow run [fuse_lo, fuse_hi) of `ops` (inference only)
     int fuse_lo = 0, fuse_hi = 0;
-    DevBuf<FusedOp> fused_dev;
-    std::vector<FusedOp> fused_host;
-    DevBuf<FusedOpH> fusedh_dev;
-    // operator table of the WHOLE net for k_unet_tile (dsg_tile.hpp: one launch per pass for small batches), rebuilt with the fused
-    // narrow run's table; tile_valid: the net has the shapes the kernel covers; opt_tile: dsg_set_option(DSG_OPT_TILE_STEP)
-    DevBuf<FusedOpH> tileops_dev;
-    std::vector<FusedOpH> tileops_host;
-    bool tile_valid = false, opt_tile = true;
+    // Everything prepare_fused builds for ONE inference context (rows, pass count, unconditional tiles, precision mode): the tables on the
+    // device, their host sources and what they were built for.  Two sets are resident.  tabs[0] serves every entry point as before.
+    // tabs[1] is the one-pass context of a sampling call whose guidance schedule has a zero (dsg_set_step_guidance): the
+    // captured step graphs of either context hold the addresses of their own set, so a call that alternates uploads nothing.  A context
+    // names its set (RunCtx::set); prepare_fused and the launch code read no other.
+    struct FusedSig { bool valid = false, sp = false, share = false; int nrows = 0, npass = 0, uncond_tiles = 0; const void* p[8] = {}; };
+    struct InferTables {
+        DevBuf<FusedOp> fused_dev;
+        std::vector<FusedOp> fused_host;
+        DevBuf<FusedOpH> fusedh_dev;
+        std::vector<FusedOpH> fusedh_host;
+        // operator table of the WHOLE net for k_unet_tile (dsg_tile.hpp: one launch per pass for small batches), rebuilt with the fused
+        // narrow run's table; tile_valid: the net has the shapes the kernel covers
+        DevBuf<FusedOpH> tileops_dev;
+        std::vector<FusedOpH> tileops_host;
+        bool tile_valid = false;
+        // what the device copy was built for (dsg_sample / dsg_unet_forward / dsg_time_op share set 0)
+        FusedSig fused_sig;
+        // LDS-resident form of the narrow run (k_fused_narrow_lds): per-operator LDS offsets, the copy list of every phase, the phases
+        DevBuf<NarrowLdsOp> nlds_ops_dev; DevBuf<NarrowLdsCopy> nlds_copies_dev; DevBuf<uint4> nlds_image;
+        std::vector<NarrowPhaseArgs> nlds_phases;
+        bool nlds_tail = false;            // the LDS form of the run also computes the 64-wide Linear at ops[fuse_hi] (kind 2)
+        bool nlds_valid = false;
+        int nlds_ncopies = 0;              // entries of nlds_copies_dev: dsg_bind_weights re-gathers the image from the re-packed arena
+        size_t nlds_image_cap = 0;         // uint4 capacity of nlds_image (grow-only: captured graphs hold the pointer)
+    } tabs[2];
+    bool opt_tile = true;             // dsg_set_option(DSG_OPT_TILE_STEP)
     bool opt_panel_half = true;       // dsg_set_option(DSG_OPT_PANEL_HALF): the 128-wide panel kernels with 16 KiB panels, two workgroups per CU
     bool opt_cfg_share = true;        // dsg_set_option(DSG_OPT_CFG_SHARE): down.0 of a two-pass step runs lin1 / lin2 once per row tile (k_panel128_duo_h)
     DevBuf<FusedOpH> fusedh_train_dev;      // the same run for the training forward (every output stored, h1/h2 saved)
     const void* fusedh_train_key[4] = {nullptr, nullptr, nullptr, nullptr}; int fusedh_train_rows = 0;
-    // inference tables (dsg_sample / dsg_unet_forward / dsg_time_op share them): what the device copy was built for
-    struct FusedSig { bool valid = false, sp = false, share = false; int nrows = 0, npass = 0, uncond_tiles = 0; const void* p[8] = {}; } fused_sig;
     DevBuf<FusedOp> ce_dev;             // condition-embedding Linear table (narrow blocks, one launch)
     std::vector<FusedOp> ce_host;
     DevBuf<CondTile> ctile_dev; int ctile_n = 0; const float* ctile_key = nullptr; size_t ctile_cap = 0;
-    std::vector<FusedOpH> fusedh_host;
-    // LDS-resident form of the narrow run (k_fused_narrow_lds): per-operator LDS offsets, the copy list of every phase, the phases
-    DevBuf<NarrowLdsOp> nlds_ops_dev; DevBuf<NarrowLdsCopy> nlds_copies_dev; DevBuf<uint4> nlds_image;
-    std::vector<NarrowPhaseArgs> nlds_phases;
-    bool nlds_tail = false;            // the LDS form of the run also computes the 64-wide Linear at ops[fuse_hi] (kind 2)
-    bool nlds_valid = false;
     // the 8-wide bottom of the net as ops [v8_lo, v8_hi) (Downsample 16 -> 8 ... Upsample 8 -> 16), or -1: computed on the vector unit
     // in float32 by the LDS form of the narrow run (dsg_narrow8.hpp); opt_v8: dsg_set_option(DSG_OPT_NARROW_VALU8)
     int v8_lo = -1, v8_hi = -1;
@@ -247,8 +268,6 @@ struct dsg_handle {
     // the section's image in global memory (V8SecL layout: raw nn.Linear matrices and parameter vectors), gathered at every bind; the LDS
     // form of the narrow run stages it as one piece, small launches and the training forward read it from L1 / L2
     DevBuf<float> v8_image; DevBuf<NarrowLdsCopy> v8_copies_dev; int v8_ncopies = 0;
-    int nlds_ncopies = 0;              // entries of nlds_copies_dev: dsg_bind_weights re-gathers the image from the re-packed arena
-    size_t nlds_image_cap = 0;         // uint4 capacity of nlds_image (grow-only: captured graphs hold the pointer)
 
     // chunked calls (dsg_sample_chunked): per-chunk Philox seeds and per-chunk renorm partials
     DevBuf<unsigned long long> seeds_dev; int seeds_cap = 0;
@@ -471,7 +490,7 @@ void free_train_workspace(dsg_handle* h) {
 
 void free_workspace(dsg_handle* h) {
     ++h->generation;
-    h->fused_sig.valid = false;
+    for (auto& t : h->tabs) t.fused_sig.valid = false;
     free_graphs(h);
     free_train_workspace(h);  // its descriptors point into the forward workspace
     h->fw = {};
@@ -594,10 +613,10 @@ bool create_device_state(dsg_handle* h) {
             h->num_cus = cus;
     }
     bool ok = h->ce_dev.alloc(h->res.size() + 1) == hipSuccess &&
-              h->fusedh_dev.alloc(h->ops.size() + 1) == hipSuccess &&
-              h->tileops_dev.alloc(h->ops.size() + 1) == hipSuccess &&
+              h->tabs[0].fusedh_dev.alloc(h->ops.size() + 1) == hipSuccess &&
+              h->tabs[0].tileops_dev.alloc(h->ops.size() + 1) == hipSuccess &&
               h->maxabs.alloc(h->params.size() + 1) == hipSuccess &&
-              h->fused_dev.alloc(2 * (h->ops.size() + 1)) == hipSuccess &&
+              h->tabs[0].fused_dev.alloc(2 * (h->ops.size() + 1)) == hipSuccess &&
               h->arena.alloc(h->arena_floats) == hipSuccess &&
               hipMemset(h->arena, 0, h->arena_floats * sizeof(float)) == hipSuccess &&
               h->tdesc_dev.alloc(h->res.size()) == hipSuccess &&

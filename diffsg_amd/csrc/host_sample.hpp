@@ -6,13 +6,21 @@ namespace {
 
 // The form of a call's steps, built once by sample_impl: one call or `chunks` independent ones of `chunk_n` elements (0: one call), with
 // per-chunk settings (`var`, chunk variants) or without, and the renorm partial sums -- one call: the handle's two partial rows; chunked:
-// [chunks][kRedBlocks] twice, one grid row per chunk.
-struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; };
+// [chunks][kRedBlocks] twice, one grid row per chunk.  `sched`: the handle holds a guidance schedule (dsg_set_step_guidance): the update
+// is the scheduled form, and a step is two-pass or one-pass (StepKind).
+struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; bool sched; };
+
+// The two contexts of a call: ctx[0] two passes (unconditional tiles first), ctx[1] the one pass of an unguided step, with the resident
+// table set of each (dsg_handle::tabs).  Only a call whose schedule has a zero builds and prepares ctx[1].
+struct StepCtxs { RunCtx ctx[2]; };
 
 // ev: DSG_SAMPLE_PROFILE's event pairs, or null.  use_hook: take the renorm hook's host callback on this step.  Never while capturing:
 // the callback enqueues a real collective (a rank whose graphs are already cached would not issue it: the all-reduces would pair up
 // wrongly or hang) and the caller's `renorm_stats` pointer would be baked into the cached graph and outlive the hook.
-int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, const StepForm& f, bool renorm, hipStream_t s, const Event* ev, bool use_hook) {
+// one_pass: an unguided step of a scheduled call -- the one-pass context and its table set; the update reads plane 0 of eps alone.
+int enqueue_step(dsg_handle* h, const StepCtxs& cs, bool one_pass, const UpdateArgs& u, const StepForm& f, bool renorm, hipStream_t s, const Event* ev,
+                 bool use_hook) {
+    const RunCtx& c = cs.ctx[one_pass ? 1 : 0];
     if (ev) {
         // DSG_SAMPLE_PROFILE: one event pair per operator.  A launch that covers several operators (the fused narrow run, a pair) is
         // booked on its first operator, the others read ~0.  f32_pairs = false preserves what this loop did before it shared the walk
@@ -27,7 +35,10 @@ int enqueue_step(dsg_handle* h, const RunCtx& c, const UpdateArgs& u, const Step
     const unsigned ublocks = (unsigned)(((u.n + 3) / 4 + 255) / 256 < 2048 ? ((u.n + 3) / 4 + 255) / 256 : 2048);
     UpdateArgs ua = u;
     ua.record_y = renorm ? 0 : 1;
-    if (f.var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
+    const float* const* gpp = h->guid_call;
+    if (f.var && f.sched) hipLaunchKernelGGL(k_update_var_sched, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, gpp);
+    else if (f.var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
+    else if (f.sched) hipLaunchKernelGGL(k_update_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp);
     else hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(256), 0, s, ua);
     if (renorm && f.var) {   // chunk variants (never with a hook): every chunk's sums, then the apply of the chunks whose count covers this step
         hipLaunchKernelGGL(k_renorm_sum, dim3(kRedBlocks, f.chunks), dim3(256), 0, s, (const float*)u.y, u.n, f.p1, f.p2, f.chunk_n);
@@ -67,6 +78,13 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     if (B < 1 || T < 1) return fail("B and T must be >= 1");
     if (!coef || !cond || !out) return fail("dsg_sample: null pointer argument");
     if (h->grid_n && T != h->grid_n) return fail("dsg_sample: the handle's step grid (dsg_set_step_grid) has %d steps, the call has T = %d", h->grid_n, T);
+    if (h->guid_n && T != h->guid_n)
+        return fail("dsg_sample: the handle's guidance schedule (dsg_set_step_guidance) has %d weights, the call has T = %d", h->guid_n, T);
+    const bool sched = h->guid_n > 0;
+    // step k of the call (step index T-1-k) is unguided: one denoiser pass
+    auto unguided = [&](int k) { return sched && h->guid_host[(size_t)(T - 1 - k)] == 0.f; };
+    bool any_one_pass = false;
+    for (int k = 0; k < T && !any_one_pass; ++k) any_one_pass = unguided(k);
     const int chunks = chunk_rows > 0 ? cdiv(B, chunk_rows) : 1;
     if (chunk_rows > 0 && (chunk_rows % 32 != 0)) return fail("dsg_sample_chunked: chunk_rows must be a multiple of 32 (a row tile)");
     if (chunks > 1 && h->renorm_fn) return fail("dsg_sample_chunked: a renorm hook (sharded global renorm) and chunking exclude each other");
@@ -131,13 +149,24 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         const VarParams vp{h->var_omega, h->var_has_renorm ? h->var_renorm.get() : nullptr, h->var_has_table ? h->var_table.get() : nullptr, n_default};
         hipLaunchKernelGGL(k_set_var, dim3(1), dim3(64), 0, s, h->var_call.get(), vp);
     }
+    if (sched) hipLaunchKernelGGL(k_set_guidance, dim3(1), dim3(64), 0, s, h->guid_call.get(), (const float*)h->guid_dev);
 
-    RunCtx c{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true};
-    c.advance_step = h->step_dev;
-    c.share_proj = split_ctx(h, c);
-    if (prepare_fused(h, c, s)) return 1;
+    StepCtxs cs{{RunCtx{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true},
+                 RunCtx{B, 1, 0, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true}}};
+    cs.ctx[1].set = 1;
+    cs.ctx[0].advance_step = cs.ctx[1].advance_step = h->step_dev;
+    cs.ctx[0].share_proj = split_ctx(h, cs.ctx[0]);       // one pass has nobody to share feature_proj with
+    if (any_one_pass) {
+        // the one-pass context's own resident set: allocated on first use, prepared (and then found current) beside set 0
+        dsg_handle::InferTables& t1 = h->tabs[1];
+        if (!t1.fusedh_dev) HIPCK(t1.fusedh_dev.alloc(h->ops.size() + 1));
+        if (!t1.tileops_dev) HIPCK(t1.tileops_dev.alloc(h->ops.size() + 1));
+        if (!t1.fused_dev) HIPCK(t1.fused_dev.alloc(2 * (h->ops.size() + 1)));
+        if (prepare_fused(h, cs.ctx[1], s)) return 1;
+    }
+    if (prepare_fused(h, cs.ctx[0], s)) return 1;
     const StepForm form{chunks, chunk_n, var, chunks > 1 ? h->red_chunks : h->red,
-                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks};
+                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks, sched};
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
@@ -148,10 +177,10 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         std::vector<Event> ev(2 * nops);
         for (auto& e : ev) HIPCK(hipEventCreate(e.put()));
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, form, k < n_renorm, s, ev.data(), true)) return 1;
+            if (enqueue_step(h, cs, unguided(k), u, form, k < n_renorm, s, ev.data(), true)) return 1;
     } else if (flags & DSG_SAMPLE_NO_GRAPH) {
         for (int k = 0; k < T; ++k)
-            if (enqueue_step(h, c, u, form, k < n_renorm, s, nullptr, true)) return 1;
+            if (enqueue_step(h, cs, unguided(k), u, form, k < n_renorm, s, nullptr, true)) return 1;
     } else {
         // The step index is a device counter and everything per call sits in device memory, so a captured step depends only on
         // the workspace (rows, chunk count) -- not on T, the seed or the schedule.  Captured once per workspace: one early
@@ -163,37 +192,49 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             G.reset();
             G.rows = B; G.chunks = chunks; G.chunk_rows = chunk_rows;
         }
+        // Under a guidance schedule the set has three kinds of step (StepKind): the scheduled update with two passes or with one.  The
+        // call is cut into runs of equal kind; none of the graphs depends on the weights, only the host's choice among them does.
         // captured lazily: only the run lengths a call replays (a one-off batch size pays for its own decomposition, not for
         // 64 steps of nodes)
-        auto graph_of = [&](int variant) -> int {
-            if (G.exec[variant]) return 0;
+        auto kind_of = [&](int k) { return !sched ? STEP_PLAIN : unguided(k) ? STEP_ONEPASS : STEP_SCHED; };
+        auto graph_of = [&](int kind, int variant) -> int {
+            GraphExec& ge = G.exec[kind][variant];
+            if (ge) return 0;
             const int run = variant == 0 ? 1 : 1 << (variant - 1);
             hipGraph_t g = nullptr;
             HIPCK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = 0;
-            for (int k = 0; k < run && !rc; ++k) rc = enqueue_step(h, c, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
+            for (int k = 0; k < run && !rc; ++k)
+                rc = enqueue_step(h, cs, kind == STEP_ONEPASS, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
-            e = hipGraphInstantiate(G.exec[variant].put(), g, nullptr, nullptr, 0);
+            e = hipGraphInstantiate(ge.put(), g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (e != hipSuccess) return fail("hipGraphInstantiate: %s", hipGetErrorString(e));
             return 0;
         };
         for (int k = 0; k < n_renorm; ++k) {
             if (h->renorm_fn) {                           // the hook calls back into the host: these (<= 4) steps run eagerly
-                if (enqueue_step(h, c, u, form, true, s, nullptr, true)) return 1;
+                if (enqueue_step(h, cs, unguided(k), u, form, true, s, nullptr, true)) return 1;
             } else {
-                if (graph_of(0)) return 1;
-                HIPCK(hipGraphLaunch(G.exec[0], s));
+                const int kind = kind_of(k);
+                if (graph_of(kind, 0)) return 1;
+                HIPCK(hipGraphLaunch(G.exec[kind][0], s));
             }
         }
-        for (int left = T - n_renorm; left > 0;) {
-            int v = kStepRunGraphs - 1;
-            while ((1 << v) > left) --v;
-            if (graph_of(1 + v)) return 1;
-            HIPCK(hipGraphLaunch(G.exec[1 + v], s));
-            left -= 1 << v;
+        for (int k = n_renorm; k < T;) {
+            const int kind = kind_of(k);
+            int left = 1;
+            while (k + left < T && kind_of(k + left) == kind) ++left;
+            k += left;
+            while (left > 0) {                      // the binary decomposition of the run
+                int v = kStepRunGraphs - 1;
+                while ((1 << v) > left) --v;
+                if (graph_of(kind, 1 + v)) return 1;
+                HIPCK(hipGraphLaunch(G.exec[kind][1 + v], s));
+                left -= 1 << v;
+            }
         }
     }
     HIPCK(hipMemcpyAsync(out, h->fw.ywork, n * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -98,7 +98,9 @@ class DDPMCore(nn.Module):
                       enqueues (consecutive calls pipeline); the flag is then sticky: the NEXT sample / sample_chunked /
                       forward on this object raises if that call's results were saturated.
           plan        a `steps.StepPlan`: run its K steps (a sub-sequence of the trained ones, or the last k + 1) instead of all T;
-                      `noise` is then (K-2, B, D) and the recorded trajectory (B, K*D).  None: all T trained steps.
+                      `noise` is then (K-2, B, D) and the recorded trajectory (B, K*D).  None: all T trained steps.  A plan with
+                      `guidance` (steps.with_guidance) guides step j with omega * g_j and runs the conditional denoiser pass alone
+                      where g_j == 0 (the recorded eps of such a step is that pass's output); DESIGN.md 16.
         """
         K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
@@ -160,6 +162,12 @@ class DDPMCore(nn.Module):
             raise ValueError(f"step plan: renorm_steps = {plan.renorm_steps} is outside 0 .. {K}")
         if not self._coef_noise_free(plan.coef):
             raise ValueError("step plan: steps 0 and 1 must be noise free (coef[:2, 3] == 0): the noise tensor has K - 2 rows")
+        if plan.guidance is not None:
+            from .steps import check_guidance
+            try:
+                check_guidance(plan.guidance, K)
+            except ValueError as e:
+                raise ValueError(f"step plan: {e}") from None
         self._check_noise(noise, K, cond.shape[0], f" for a plan of {K} steps")
         return K
 
@@ -222,6 +230,29 @@ class DDPMCore(nn.Module):
         nat.step_grid = (hd, plan, coef)
         return coef
 
+    def _use_guidance(self, hd, g, dev):
+        """Make handle `hd` hold the guidance schedule `g` (None: none).  What the handle holds is remembered beside it, as `_use_plan`
+        does: repeated calls with the same weights set nothing (setting them synchronises the device), a plan without guidance after one
+        with it removes them."""
+        import ctypes
+        nat = self.model._native
+        held = nat.step_guidance                         # (handle, the weights, their tensor and its version)
+        if held is not None and held[0] != hd:
+            held = None
+        if g is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_step_guidance(hd, None, 0))
+                nat.step_guidance = None
+            return
+        if held is not None and held[2] is g and held[3] == g._version:      # the same tensor, unchanged: nothing to convert or compare
+            return
+        key = tuple(g.detach().cpu().to(torch.float32).tolist())
+        if held is None or held[1] != key:
+            arr = (ctypes.c_float * len(key))(*key)
+            with torch.cuda.device(dev):          # a refused or failed call leaves what the handle holds, and this record of it, unchanged
+                _lib.check(_lib.lib().dsg_set_step_guidance(hd, arr, len(key)))
+        nat.step_guidance = (hd, key, g, g._version)
+
     def _resolve_variants(self, variants, cond, noise):
         """[(omega, plan)] of a list of variants with `None` plans replaced by the identity plan (all T trained steps, the trained table's
         own rows, min(T, 4) renorm steps), and the step count K they share -- after the checks that need no device: every plan passes
@@ -248,6 +279,9 @@ class DDPMCore(nn.Module):
             if not ((plan.taus is first.taus or tuple(plan.taus) == tuple(first.taus)) and (plan.t is first.t or torch.equal(plan.t.cpu(), first.t.cpu()))):
                 raise ValueError(f"variant {k} has another step grid (taus / t) than variant 0: the variants of one call share the time "
                                  "table and may differ in omega, coef and renorm_steps")
+            if not _same_guidance(plan.guidance, first.guidance):
+                raise ValueError(f"variant {k} has another guidance schedule than variant 0: the variants of one call share `guidance` "
+                                 "(the number of denoiser passes is per launch, not per chunk)")
             out.append((float(omega), plan))
         return out, len(out[0][1].taus)
 
@@ -272,6 +306,7 @@ class DDPMCore(nn.Module):
             grid = nat.step_grid
             if not (grid is not None and grid[0] == hd and torch.equal(grid[1].t, plan0.t)):   # the renorm count of the grid is not read
                 self._use_plan(hd, plan0, dev)
+        self._use_guidance(hd, plan0.guidance, dev)           # the schedule the variants share
         # the distinct coefficient tensors, stacked once
         coefs, table = [], []
         for _, p in chunks:
@@ -310,6 +345,7 @@ class DDPMCore(nn.Module):
             return out                     # no rows, nothing to launch (the reference's loop runs on empty tensors)
         self._use_variants(hd, None, dev)  # a sample() call is no chunked call: per-chunk settings of an earlier one go
         coef = self._use_plan(hd, plan, dev)
+        self._use_guidance(hd, None if plan is None else plan.guidance, dev)
         flags = 2 if profile else (0 if use_graph else 1)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().dsg_sample_rec(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, seed, float(omega), _lib.ptr(coef), T,
@@ -335,8 +371,8 @@ class DDPMCore(nn.Module):
         `seeds` = one Philox seed per chunk (default: drawn from torch's global generator, one per chunk, in chunk order).
         `plan`: as in `sample`, the same plan for every chunk.
         `variants`: one `(omega, plan)` per chunk (plan None: all T trained steps) instead of `omega` and `plan` -- chunk k is then
-        `self.sample(cond[...], omega_k, seed=seeds[k], plan=plan_k)` bit for bit.  The plans of one call share `taus` and `t` and may
-        differ in `coef` and `renorm_steps` (`steps.with_renorm`); DESIGN.md 15."""
+        `self.sample(cond[...], omega_k, seed=seeds[k], plan=plan_k)` bit for bit.  The plans of one call share `taus`, `t` and
+        `guidance` and may differ in `coef` and `renorm_steps` (`steps.with_renorm`); DESIGN.md 15, 16."""
         import ctypes
         if variants is not None:
             if plan is not None:
@@ -380,6 +416,7 @@ class DDPMCore(nn.Module):
             if variants is None:
                 self._use_variants(hd, None, dev)
                 coef = self._use_plan(hd, plan, dev)
+                self._use_guidance(hd, None if plan is None else plan.guidance, dev)
             else:
                 coef = self._use_variants(hd, variants, dev)      # [tables][K][4]; `omega` is not read by the call
             with torch.cuda.device(dev):
@@ -729,6 +766,12 @@ def best_calls(n, B, chunk_rows, max_rows, variants=None, omega=1.0, plan=None):
             o, p = variants[r0 % len(variants)] if variants else (omega, plan)
             calls.append(BestCall(kind, r0, 1, u, o, p, None, sd))
     return calls
+
+
+def _same_guidance(a, b):
+    if a is None or b is None:
+        return a is b
+    return a is b or (tuple(a.shape) == tuple(b.shape) and torch.equal(a.cpu(), b.cpu()))
 
 
 def _is_trained_grid(plan, T):

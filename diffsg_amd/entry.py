@@ -8,6 +8,9 @@ The sampler options of `load_test_msr`, `load_test_co` and `load_test_nu`, beyon
             the reference.
   variants  a list of (omega, plan) sampler settings cycled over the `repeats` rounds (round r runs variants[r % len(variants)],
             DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the single-setting spelling and are not read then.
+            A plan of a variant may carry a guidance schedule (`steps.with_guidance(plan_or_model, g)`, DESIGN.md 16: step j guided with
+            omega * g_j, one denoiser pass where g_j == 0); the variants of one call share it.  The entry points have no keyword of their
+            own for it: their signatures are pinned.
 """
 from __future__ import annotations
 

@@ -5,8 +5,10 @@ A `StepPlan` is what a `DDPM.sample(..., plan=...)` call needs beyond the model:
 
     y <- (y - c1 * eps) * c2 + c3 * z,        z used iff c4 != 0
 
-and how many of the first steps of a call standardise y (`renorm_steps`; classifier_free_MSR.py:136-137).  Step index K-1 runs first,
-0 last.  Three constructors (and `with_renorm(plan, n)`: the same plan with another renorm count):
+and how many of the first steps of a call standardise y (`renorm_steps`; classifier_free_MSR.py:136-137) and, optionally, a guidance
+weight per step (`guidance`, DESIGN.md 16: step j is guided with omega * g_j, and where g_j == 0 the unconditional denoiser pass is not
+run at all).  Step index K-1 runs first, 0 last.  Three constructors (and `with_renorm(plan, n)` / `with_guidance(plan, g)`: the same
+plan with another renorm count / guidance schedule; `guidance_interval` and `guidance_every` make the two usual 0/1 schedules):
 
   strided(ddpm, K)     K < T steps of the reference's own (ancestral) update rule, re-derived for the sub-sequence;
   ddim(ddpm, K, eta)   DDIM (Song et al. 2021, eq. 12) on the same grid; deterministic at eta = 0;
@@ -20,6 +22,7 @@ omega = 500).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -31,6 +34,7 @@ class StepPlan:
     t: torch.Tensor             # float32 [K]: taus / T, as the reference divides an int64 tensor (MSR.py:126)
     coef: torch.Tensor          # float32 [K, 4]
     renorm_steps: int           # the first `renorm_steps` steps of a call standardise y
+    guidance: Optional[torch.Tensor] = None     # float32 [K], finite, >= 0: step j uses omega * guidance[j]; 0: one denoiser pass; None: all ones
 
     @property
     def K(self):
@@ -124,7 +128,46 @@ def with_renorm(plan_or_ddpm, renorm_steps):
     plan = plan_or_ddpm if isinstance(plan_or_ddpm, StepPlan) else strided(plan_or_ddpm, plan_or_ddpm.T)
     if int(renorm_steps) != renorm_steps or not 0 <= int(renorm_steps) <= plan.K:
         raise ValueError(f"with_renorm: renorm_steps must be an integer in [0, {plan.K}], got {renorm_steps}")
-    return StepPlan(plan.taus, plan.t, plan.coef, int(renorm_steps))
+    return StepPlan(plan.taus, plan.t, plan.coef, int(renorm_steps), plan.guidance)
+
+
+def with_guidance(plan_or_ddpm, g):
+    """The plan with the guidance schedule `g` (K weights, finite and >= 0; None: none) and everything else shared, the `coef` tensor
+    included; for a `DDPM` the identity plan -- all T trained steps, the trained table's own rows -- with that schedule.  Step j is guided
+    with omega * g[j]; a step with g[j] == 0 runs the conditional denoiser pass alone."""
+    plan = plan_or_ddpm if isinstance(plan_or_ddpm, StepPlan) else strided(plan_or_ddpm, plan_or_ddpm.T)
+    if g is not None:
+        g = torch.as_tensor(g, dtype=torch.float32).detach().cpu().reshape(-1).contiguous()
+        check_guidance(g, plan.K)
+    return StepPlan(plan.taus, plan.t, plan.coef, plan.renorm_steps, g)
+
+
+def check_guidance(g, K):
+    """Raise ValueError unless `g` is a float32 tensor of K finite weights >= 0."""
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != (K,):
+        raise ValueError(f"guidance must be a float32 tensor of shape ({K},), one weight per step")
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("guidance weights must be finite")
+    if bool((g < 0).any()):
+        raise ValueError("guidance weights must be >= 0")
+
+
+def guidance_interval(K, lo, hi):
+    """float32 [K]: 1 on the step indices lo .. hi (inclusive), 0 elsewhere -- guidance in a limited interval (Kynkaanniemi et al. 2024)."""
+    K, lo, hi = int(K), int(lo), int(hi)
+    if not 0 <= lo <= hi <= K - 1:
+        raise ValueError(f"guidance_interval: need 0 <= lo <= hi <= K - 1 = {K - 1}, got lo = {lo}, hi = {hi}")
+    g = torch.zeros(K, dtype=torch.float32)
+    g[lo:hi + 1] = 1.0
+    return g
+
+
+def guidance_every(K, n, phase=0):
+    """float32 [K]: 1 on the step indices j with j % n == phase, 0 elsewhere (n = 2: the even indices; n = 2, phase = 1: the odd ones)."""
+    K, n, phase = int(K), int(n), int(phase)
+    if K < 1 or n < 1 or not 0 <= phase < n:
+        raise ValueError(f"guidance_every: need K >= 1, n >= 1 and 0 <= phase < n, got K = {K}, n = {n}, phase = {phase}")
+    return (torch.arange(K) % n == phase).to(torch.float32)
 
 
 def make(ddpm, steps=None, sampler="strided", eta=0.0):

@@ -205,6 +205,22 @@ int dsg_sample_chunked(dsg_handle* h, const float* cond, const float* y_T, const
  * the grid does not synchronise.  The captured step graphs do not depend on the grid and are kept. */
 int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_steps);
 
+/* Guidance schedule: one weight per step of a sampling call.  `g_host` is a HOST array of n finite floats >= 0, indexed
+ * like `coef` (index n-1 runs first).  While it is held, step j of dsg_sample / dsg_sample_rec / dsg_sample_chunked is guided with
+ *     omega_j = omega * g_host[j]                 (one float32 multiplication, round to nearest)
+ * in the expression of the unscheduled step, eps = (1 + omega_j) eps1 - omega_j eps0: a weight of 1 gives the bits of the unscheduled
+ * step.  With chunk variants omega is the chunk's.  Where g_host[j] == 0 the step is UNGUIDED: eps = eps1, and the unconditional
+ * denoiser pass is not launched at all (one pass over ceil(B / 32) row tiles, every tile with the condition term).  Everything else of
+ * such a step is unchanged: coefficient row, Philox stream and index, injected-noise row, early renorm, trajectory record (rec_eps
+ * carries eps1), and the device step counter moves as on any step.
+ * g_host == NULL or n == 0 removes the setting.  Refused: n < 0, a negative or non-finite weight.  With the setting held the three
+ * sampling entry points fail before anything is enqueued when T != n.  dsg_unet_forward, dsg_time_op and the training steps ignore it.
+ * The weights are copied into a device buffer the handle owns (and kept on the host, where the launch sequence is chosen).  Like the
+ * other settings calls this one takes no stream: it selects the handle's device itself and synchronises that device before it overwrites
+ * the buffer (an enqueued call may still read it); removing the setting overwrites nothing and does not synchronise.  The captured step
+ * graphs depend neither on the values nor on the buffer: setting, changing or removing the schedule drops none. */
+int dsg_set_step_guidance(dsg_handle* h, const float* g_host, int n);
+
 /* Chunk variants: a per-chunk sampler setting for dsg_sample_chunked.  Every chunk of a chunked call is an independent sample() call; with
  * this per-handle setting the calls may also differ in omega, in the coefficient table and in the number of early renormalised steps:
  *   omega_host   HOST array [chunks]: chunk c is guided with omega_host[c];
