@@ -252,6 +252,38 @@ __device__ __forceinline__ void acc_stats(const f32x16 (&acc)[NT], int h, float&
     m2 = xhalf_sum(q);
 }
 
+// Moves between an accumulator-resident tile and its fragment form: 8-feature group G of the tile is four consecutive registers of
+// every lane (a float4); in memory a group is 256 floats, `p` = tile base + lane * 4.
+template <int NT>
+__device__ __forceinline__ float4 acc_f4(const f32x16 (&a)[NT], int G) {
+    return make_float4(a[G >> 2][4 * (G & 3)], a[G >> 2][4 * (G & 3) + 1], a[G >> 2][4 * (G & 3) + 2], a[G >> 2][4 * (G & 3) + 3]);
+}
+template <int NT>
+__device__ __forceinline__ void acc_add_f4(f32x16 (&a)[NT], int G, const float4 v) {
+    a[G >> 2][4 * (G & 3) + 0] += v.x; a[G >> 2][4 * (G & 3) + 1] += v.y;
+    a[G >> 2][4 * (G & 3) + 2] += v.z; a[G >> 2][4 * (G & 3) + 3] += v.w;
+}
+template <int NG, int NT>
+__device__ __forceinline__ void acc_load(f32x16 (&a)[NT], const float* __restrict__ p /* tile base + lane*4 */) {
+#pragma unroll
+    for (int G = 0; G < NT * 4; ++G) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (G < NG) v = ld4(p + (size_t)G * 256);
+        a[G >> 2][4 * (G & 3) + 0] = v.x; a[G >> 2][4 * (G & 3) + 1] = v.y;
+        a[G >> 2][4 * (G & 3) + 2] = v.z; a[G >> 2][4 * (G & 3) + 3] = v.w;
+    }
+}
+template <int NG, int NT>
+__device__ __forceinline__ void acc_load_add(f32x16 (&a)[NT], const float* __restrict__ p) {
+#pragma unroll
+    for (int G = 0; G < NG; ++G) acc_add_f4<NT>(a, G, ld4(p + (size_t)G * 256));
+}
+template <int NG, int NT>
+__device__ __forceinline__ void acc_store(const f32x16 (&a)[NT], float* __restrict__ p) {
+#pragma unroll
+    for (int G = 0; G < NG; ++G) st4(p + (size_t)G * 256, acc_f4<NT>(a, G));
+}
+
 // B operands for a chain whose input is an accumulator: act = silu(LN(acc)), then MFMA into `out`.
 // ResidualBlock stages 2 and 3 (UNetCF.py:92,94).
 // First-group operands of a register-fed chain, issued by the caller well before the chain starts (narrow blocks are

@@ -359,44 +359,71 @@ __device__ __forceinline__ void panel_pipe_s(f32x16 (&acc)[4], const uint4* pn /
 #ifndef DSG_PANEL_TRAIL_PRIO
 #define DSG_PANEL_TRAIL_PRIO 1
 #endif
-template <bool SCLIN, int EPI, int NTO, int STEPS = 4>
-__global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const BlockLinArgsH A, const int ngroups) {
-    constexpr int N = 128, NT = 4, NG = 16;
-    constexpr int PW = panel_pw(STEPS), PU4 = panel_u4(STEPS), NTHR = 64 * PW;
-    constexpr int KS1 = SCLIN ? 16 : 8, P1 = KS1 / STEPS, P2 = 8 / STEPS, NE = SCLIN ? 16 : 8;   // k16-steps of stage 1; items of the shortcut / residual read
-    constexpr int NTOP = NTO <= 1 ? 1 : (NTO == 2 ? 2 : 4), ESTEPS = 4 * STEPS / NTOP;    // epilogue Linear: k16-steps per panel (8 needed)
-    constexpr int EPANELS = EPI == 0 ? 0 : (ESTEPS >= 8 ? 1 : 8 / ESTEPS);
-    constexpr int PA = P1, PB = PA + P2, PD = PB + P2, PE = PD + (SCLIN ? P1 : 0), NP = PE + EPANELS;
-    __shared__ uint4 lds[panel_lds_u4(STEPS) + (STEPS == 4 ? kPanelStampU4 : 0)];
-#ifdef DSG_CYCLE_STAMPS
-    unsigned long long* const stamp_lds = reinterpret_cast<unsigned long long*>(lds + panel_lds_u4(STEPS));
-    int stamp_k = 0;
-    constexpr bool STAMPED = (DSG_STAMP_DOWN0 ? !SCLIN : SCLIN) && EPI == 0 && STEPS == 4;
-#endif
-    float* const vec = reinterpret_cast<float*>(lds + 2 * PU4 + PW * kPrivSlots * kPrivU4);
-    float* const g1v = vec, * const b1v = vec + kLnLdsW1, * const v2 = vec + 2 * kLnLdsW1;
-    float* const g2v = v2, * const b2v = v2 + 128, * const g3v = v2 + 256, * const b3v = v2 + 384, * const tbv = v2 + 512, * const c2v = v2 + 640,
-         * const c3v = v2 + 768, * const gLv = v2 + 896, * const bLv = v2 + 1024, * const biasLv = v2 + 1152;
-    const BlockArgsH& ah = A.b;
-    const BlockArgs& a = ah.b;
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int stride = gridDim.x;
-#ifdef DSG_CYCLE_STAMPS
-    // the clock the chip holds under THIS kernel: shader cycles (s_memtime) against the constant 100 MHz counter (s_memrealtime)
-    const unsigned long long clk_t0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    // Waves w and w + 4 share a SIMD.  Both run the same program (every panel's MFMA stream carries the operand preparation of
-    // the next step between its MFMAs, panel_pipe_s); the younger half gets a static priority: at equal priority the older wave
-    // of a SIMD wins every arbitration, finishes a panel ~1 400 cycles before its partner and idles at the barrier while the
-    // partner runs alone (cycle stamps: 3 000 against 4 400 cycles per LayerNorm panel).  MI355X guide, "two waves per SIMD".
-    // (STEPS = 2: the workgroup has one wave per SIMD; its SIMD partners belong to the CU's other workgroup)
-    const bool lead = wave < 4;
-    if (STEPS == 4 && !lead) __builtin_amdgcn_s_setprio(DSG_PANEL_TRAIL_PRIO);
-    constexpr float kL2 = -1.44269504088896341f;
 
-    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e)
-    {
+// ---- The block program of one persistent workgroup, in pieces.  k_panel128_h and k_panel128_duo_h below are compositions of these: what
+// a kernel keeps to itself is its table of weight panels (`panel_src`), the positions of its private stream (which item is requested at
+// which consume site) and the parts only it has.  Two rules bind every composition:
+//   * every wave, live or idle, meets the same sequence of panel_begin() barriers per tile group;
+//   * `since_w` counts exactly the private-stream DMA operations issued behind the pending panel: whoever calls priv_issue() between two
+//     panel_begin() calls adds 2 to it.
+// All members are compile-time unrolled code on scalars of the kernel: nothing of this struct lives in memory.
+template <int STEPS, bool STAMPED>
+struct PanelWg {
+    static constexpr int N = 128, NT = 4, NG = 16;
+    static constexpr int PW = panel_pw(STEPS), PU4 = panel_u4(STEPS), NTHR = 64 * PW;
+    static constexpr float kL2 = -1.44269504088896341f;
+    int lane, h, j, wave;
+    // per-feature vectors in LDS; gLv / bLv / biasLv: those of a consuming Linear (k_panel128_h's epilogue)
+    float *g1v, *b1v, *g2v, *b2v, *g3v, *b3v, *tbv, *c2v, *c3v, *gLv, *bLv, *biasLv;
+    PanelCtx c;
+    int since_w;
+#ifdef DSG_CYCLE_STAMPS
+    unsigned long long* stamp_lds;
+    int stamp_k;
+    unsigned long long clk_t0, clk_r0;
+#endif
+    __device__ __forceinline__ void stamp(int tag) { DSG_PSTAMP(tag); }
+
+    // the carve-up of `lds` (two weight buffers | private slots | vectors | stamps) and this wave's place in it
+    __device__ __forceinline__ void init(uint4* lds) {
+        lane = threadIdx.x & 63; h = lane >> 5; j = lane & 31;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#ifdef DSG_CYCLE_STAMPS
+        stamp_lds = reinterpret_cast<unsigned long long*>(lds + panel_lds_u4(STEPS));
+        stamp_k = 0;
+        // the clock the chip holds under THIS kernel: shader cycles (s_memtime) against the constant 100 MHz counter (s_memrealtime)
+        clk_t0 = __builtin_readcyclecounter(); clk_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        // Waves w and w + 4 share a SIMD.  Both run the same program (every panel's MFMA stream carries the operand preparation of
+        // the next step between its MFMAs, panel_pipe_s); the younger half gets a static priority: at equal priority the older wave
+        // of a SIMD wins every arbitration, finishes a panel ~1 400 cycles before its partner and idles at the barrier while the
+        // partner runs alone (cycle stamps: 3 000 against 4 400 cycles per LayerNorm panel).  MI355X guide, "two waves per SIMD".
+        // (STEPS = 2: the workgroup has one wave per SIMD; its SIMD partners belong to the CU's other workgroup)
+        if (STEPS == 4 && wave >= 4) __builtin_amdgcn_s_setprio(DSG_PANEL_TRAIL_PRIO);
+        float* const vec = reinterpret_cast<float*>(lds + 2 * PU4 + PW * kPrivSlots * kPrivU4);
+        float* const v2 = vec + 2 * kLnLdsW1;
+        g1v = vec; b1v = vec + kLnLdsW1;
+        g2v = v2; b2v = v2 + 128; g3v = v2 + 256; b3v = v2 + 384; tbv = v2 + 512; c2v = v2 + 640; c3v = v2 + 768;
+        gLv = v2 + 896; bLv = v2 + 1024; biasLv = v2 + 1152;
+        const unsigned lds0 = (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void*)lds;
+        c.lane16 = (unsigned)lane * 16u; c.lane4 = (unsigned)lane * 4u;
+        c.w_lds = lds0 + (unsigned)wave * 4096u;
+        c.w_rd = lds0 + (unsigned)lane * 16u;
+        c.p_lds = lds0 + 2u * PU4 * 16u + (unsigned)wave * (kPrivSlots * 2048u);
+        c.wrd = lds + lane;
+        c.prd = lds + 2 * PU4 + wave * (kPrivSlots * kPrivU4) + lane;
+        c.q = 0; c.islot = 0; c.cslot = 0;
+        // DMA operations of the private stream issued BEHIND the pending panel's own four.  (Rounds 2-4 started this at 8 for "the four
+        // private requests of the prologue" -- but those go out IN FRONT of panel 0, so the first panel of a launch was waited for with
+        // vmcnt(8) while it could be among the eight youngest operations: nothing ordered its arrival before the first reads.  It never
+        // showed with one workgroup per CU -- panel 0 is requested a statistics merge and an operand preparation ahead -- and did within
+        // minutes with two (round 5, the STEPS = 2 form: a handful of first-group tiles wrong, run-to-run different).)
+        since_w = 0;
+    }
+
+    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e); `more(i)`: further vectors of feature i
+    template <typename More>
+    __device__ __forceinline__ void stage_vectors(const BlockArgs& a, More&& more) {
         const int n1 = ln1_extent(a);
         for (int i = threadIdx.x; i < n1; i += NTHR) { g1v[i] = a.gamma1[i] * kL2; b1v[i] = a.beta1[i] * kL2; }
         if (threadIdx.x < 128) {
@@ -404,14 +431,183 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             g2v[i] = a.gamma2[i] * kL2; b2v[i] = a.beta2[i] * kL2; g3v[i] = a.gamma3[i] * kL2; b3v[i] = a.beta3[i] * kL2;
             c2v[i] = a.c2[i]; c3v[i] = a.c3[i];
             tbv[i] = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + i];
-            if (EPI == 2) { gLv[i] = A.l.l.gamma[i] * kL2; bLv[i] = A.l.l.beta[i] * kL2; }
-            if (EPI != 0) biasLv[i] = i < NTO * 32 ? A.l.l.bias[i] : 0.f;
+            more(i);
+        }
+        __syncthreads();                   // no DMA is in flight yet: a plain barrier
+    }
+
+    // prologue: the first four private items of this wave's first tile (statistics, three stage-1 items), then panel 0 into buffer 0
+    __device__ __forceinline__ void prologue(const char* st0, const char* st1, const char* x0, const uint4* panel0) {
+        priv_issue_stats(c, st0, st1);
+        priv_issue(c, x0);
+        priv_issue(c, x0 + 2048);
+        priv_issue(c, x0 + 4096);
+        glds_quad_s(c.lane16, panel0, c.w_lds);
+    }
+
+    // One barrier per panel: my pieces of the panel have landed (counted wait: `since_w` DMA operations of the private stream
+    // went out behind them); everyone is done with the other buffer; refill that one with the panel after this (`next`: the block
+    // program repeats for the next tile group; the request behind the launch's last panel is redundant and drained at the end).
+    // Returns the buffer to read.
+    __device__ __forceinline__ int panel_begin(const uint4* next) {
+        if (since_w >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+        else if (STEPS < 4 && since_w >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");   // half panels: two items per panel
+        else if (since_w >= 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const int rd = c.q & 1;
+        glds_quad_s(c.lane16, next, c.w_lds + (unsigned)((c.q + 1) & 1) * (PU4 * 16u));
+        since_w = 0;
+        ++c.q;
+        return rd;
+    }
+
+    // ---- step 0 of a stage is prepared on its own (it needs the stage's row statistics): from a private slot, from accumulators
+    __device__ __forceinline__ BOp step0_mem(const uint4* rd, const float* gv, const float* bv, float cc, float dd) {
+        const float4 xa = __builtin_bit_cast(float4, rd[0]), xb = __builtin_bit_cast(float4, rd[64]);
+        const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+        return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
+    }
+    __device__ __forceinline__ BOp step0_reg(const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd) {
+        const float x[8] = {in[0][0], in[0][1], in[0][2], in[0][3], in[0][4], in[0][5], in[0][6], in[0][7]};
+        return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
+    }
+    static __device__ __forceinline__ const uint4* no_consume(int) { return nullptr; }
+    static __device__ __forceinline__ const uint4* none_n() { return nullptr; }
+
+    // ---- stage 1: memory-fed, LayerNorm + SiLU, P1 panels.  `b0`: step 0's operand (prepared on its own, or carried in from the
+    // previous tile's last panel); every other step is prepared under the MFMAs of the step before it.  consume_s1(S): wait for the item
+    // of step S and request the one four places ahead; refill(p): the panel requested behind panel p's barrier.
+    template <int P1, typename Consume, typename Refill>
+    __device__ __forceinline__ void stage1(f32x16 (&acc1)[NT], BOp b0, float cc, float dd, Consume&& consume_s1, Refill&& refill) {
+#pragma unroll
+        for (int p = 0; p < P1; ++p) {
+            const int bi = panel_begin(refill(p));
+            stamp(0x14);
+            BOp bc;
+            const NextPrep nx{&acc1, STEPS * (p + 1), g1v, b1v, cc, dd, nullptr, nullptr};
+            auto cs = [&](int jj) { return consume_s1(STEPS * p + 1 + jj); };
+            auto cn = [&]() { return consume_s1(STEPS * p + STEPS); };
+            if (p + 1 < P1) {
+                if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
+                else panel_pipe_s<false, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
+                b0 = bc;
+            } else {
+                if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
+                else panel_pipe_s<false, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
+            }
+            stamp(0x12);
         }
     }
+
+    // ---- a register-fed stage (input: the accumulators `in` of the stage before; stamps TAG + 0 / 1 / 4 / 2).
+    // reg_head: row statistics of `in`, the LayerNorm constants, step 0's operand.
+    template <int TAG>
+    __device__ __forceinline__ BOp reg_head(const f32x16 (&in)[NT], const float* gv, const float* bv, float& cc, float& dd) {
+        float mean, m2;
+        acc_stats<N, NT>(in, h, mean, m2);
+        const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps);
+        cc = rstd; dd = -mean * rstd;
+        stamp(TAG);
+        BOp b0 = step0_reg(in, gv, bv, cc, dd);
+        asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
+        stamp(TAG + 1);
+        return b0;
+    }
+    // reg_panels: the stage's first NPAN panels, each preparing the next one's first operand under its last step; `b0` enters as the
+    // operand of panel 0 and leaves as that of panel NPAN.  (All but the last panel of a stage: what is prepared under the last panel
+    // differs by stage.)
+    template <int NPAN, int TAG, typename Refill>
+    __device__ __forceinline__ void reg_panels(f32x16 (&out)[NT], const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd, BOp& b0,
+                                               Refill&& refill) {
+#pragma unroll
+        for (int p = 0; p < NPAN; ++p) {
+            const int bi = panel_begin(refill(p));
+            stamp(TAG + 4);
+            BOp bc;
+            const NextPrep nx{&in, STEPS * (p + 1), gv, bv, cc, dd, nullptr, nullptr};
+            if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(out, c.wrd + bi * PU4, b0, bc, in, STEPS * p, gv, bv, cc, dd, h, no_consume, nx, none_n);
+            else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(out, c.wrd + bi * PU4, b0, bc, in, STEPS * p, gv, bv, cc, dd, h, no_consume, nx, none_n);
+            b0 = bc;
+            stamp(TAG + 2);
+        }
+    }
+    // reg_last: the last panel (k16-steps 8 - STEPS .. 7) of a stage with nothing to prepare under its last step
+    template <int TAG>
+    __device__ __forceinline__ void reg_last(f32x16 (&out)[NT], const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd, const BOp& b0,
+                                             const uint4* next) {
+        const int bi = panel_begin(next);
+        stamp(TAG + 4);
+        BOp bn;
+        panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(out, c.wrd + bi * PU4, b0, bn, in, 8 - STEPS, gv, bv, cc, dd, h, no_consume,
+                                                        NextPrep{&in, 0, gv, bv, cc, dd, nullptr, nullptr}, none_n);
+        stamp(TAG + 2);
+    }
+
+    // ---- eight private items (one 128-wide tile: the condition embedding, the residual re-read) added into four accumulator tiles;
+    // ahead(i): the request that goes out behind item i (the item kPrivDist places further down the caller's stream, + 2 on since_w)
+    template <typename Ahead>
+    __device__ __forceinline__ void priv_add8(f32x16 (&acc)[NT], Ahead&& ahead) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint4* rd = priv_consume(c);
+            const float4 v0 = __builtin_bit_cast(float4, rd[0]), v1 = __builtin_bit_cast(float4, rd[64]);
+            ahead(i);
+            acc_add_f4<NT>(acc, 2 * i, v0);
+            acc_add_f4<NT>(acc, 2 * i + 1, v1);
+        }
+    }
+
+    // ---- row statistics of a finished tile and, where `store`, both to memory as tile `tile` of the block's output
+    __device__ __forceinline__ void stats_store(const f32x16 (&acc)[NT], const BlockArgs& a, int tile, bool store, float& xmean, float& xm2) {
+        acc_stats<N, NT>(acc, h, xmean, xm2);
+        if (store) {
+            if (h == 0) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + j] = make_float2(xmean, xm2);
+            acc_store<NG, NT>(acc, a.out + (size_t)tile * NG * 256 + lane * 4);
+        }
+    }
+
+    // ---- end of the launch
+    __device__ __forceinline__ void finish() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stream's last requests are redundant: nothing may land in LDS after the end
+#ifdef DSG_CYCLE_STAMPS
+        if (STAMPED && blockIdx.x == 0) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            for (int k = lane; k < 128; k += 64) dsg_stamp_buf[wave * 128 + k] = k < stamp_k ? stamp_lds[wave * 128 + k] : 0ull;
+            if (threadIdx.x == 0) {
+                dsg_stamp_buf[kPW * 128 + 0] = clk_t0; dsg_stamp_buf[kPW * 128 + 1] = clk_r0;
+                dsg_stamp_buf[kPW * 128 + 2] = __builtin_readcyclecounter(); dsg_stamp_buf[kPW * 128 + 3] = __builtin_amdgcn_s_memrealtime();
+                dsg_stamp_n = kPW * 128 + 4;
+            }
+        }
+#endif
+    }
+};
+
+template <bool SCLIN, int EPI, int NTO, int STEPS = 4>
+__global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const BlockLinArgsH A, const int ngroups) {
+    constexpr int NT = 4;
+    constexpr int PW = panel_pw(STEPS), PU4 = panel_u4(STEPS);
+    constexpr int KS1 = SCLIN ? 16 : 8, P1 = KS1 / STEPS, P2 = 8 / STEPS, NE = SCLIN ? 16 : 8;   // k16-steps of stage 1; items of the shortcut / residual read
+    constexpr int NTOP = NTO <= 1 ? 1 : (NTO == 2 ? 2 : 4), ESTEPS = 4 * STEPS / NTOP;    // epilogue Linear: k16-steps per panel (8 needed)
+    constexpr int EPANELS = EPI == 0 ? 0 : (ESTEPS >= 8 ? 1 : 8 / ESTEPS);
+    constexpr int PA = P1, PB = PA + P2, PD = PB + P2, PE = PD + (SCLIN ? P1 : 0), NP = PE + EPANELS;
+    __shared__ uint4 lds[panel_lds_u4(STEPS) + (STEPS == 4 ? kPanelStampU4 : 0)];
+    PanelWg<STEPS, ((DSG_STAMP_DOWN0 ? !SCLIN : SCLIN) && EPI == 0 && STEPS == 4)> w;
+    w.init(lds);
+    PanelCtx& c = w.c;
+    int& since_w = w.since_w;
+    const BlockArgsH& ah = A.b;
+    const BlockArgs& a = ah.b;
+    const int lane = w.lane, h = w.h, j = w.j, wave = w.wave;
+    const int stride = gridDim.x;
+    w.stage_vectors(a, [&](int i) {            // + the vectors of the epilogue Linear
+        if (EPI == 2) { w.gLv[i] = A.l.l.gamma[i] * w.kL2; w.bLv[i] = A.l.l.beta[i] * w.kL2; }
+        if (EPI != 0) w.biasLv[i] = i < NTO * 32 ? A.l.l.bias[i] : 0.f;
+    });
     const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
     float invL = 0.f;
     if (EPI != 0) invL = A.l.kc[EPI == 2 ? 1 : 0];
-    __syncthreads();                   // no DMA is in flight yet: a plain barrier
 
     // ---- this wave's 4 KiB of every weight panel: (out tile, two of its STEPS k16-steps)
     const int wnt = wave / (STEPS / 2), wsub = wave % (STEPS / 2);
@@ -434,48 +630,10 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
         if (p < PE) return wsp + (size_t)(p - PD) * (128 * STEPS);
         return wlp + (ESTEPS < 8 ? (size_t)(p - PE) * (128 * ESTEPS) : 0);
     };
-
-    const unsigned lds0 = (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void*)lds;
-    PanelCtx c;
-    c.lane16 = (unsigned)lane * 16u; c.lane4 = (unsigned)lane * 4u;
-    c.w_lds = lds0 + (unsigned)wave * 4096u;
-    c.w_rd = lds0 + (unsigned)lane * 16u;
-    c.p_lds = lds0 + 2u * PU4 * 16u + (unsigned)wave * (kPrivSlots * 2048u);
-    c.wrd = lds + lane;
-    c.prd = lds + 2 * PU4 + wave * (kPrivSlots * kPrivU4) + lane;
-    c.q = 0; c.islot = 0; c.cslot = 0;
-
-    // prologue: panel 0 into buffer 0 and the first four private items of this wave's first tile
     {
         const TilePtrs cur = tile_ptrs<SCLIN, PW>(a, blockIdx.x < ngroups ? blockIdx.x : 0, wave);
-        priv_issue_stats(c, cur.st0, cur.st1);
-        priv_issue(c, cur.x0);
-        priv_issue(c, cur.x0 + 2048);
-        priv_issue(c, cur.x0 + 4096);
+        w.prologue(cur.st0, cur.st1, cur.x0, panel_src(0));
     }
-    glds_quad_s(c.lane16, panel_src(0), c.w_lds);
-
-    // One barrier per panel: my pieces of the panel have landed (counted wait: `since_w` DMA operations of the private stream
-    // went out behind them); everyone is done with the other buffer; refill that one with the panel after this (`next`: the block
-    // program repeats for the next tile group; the request behind the launch's last panel is redundant and drained at the end).
-    // DMA operations of the private stream issued BEHIND the pending panel's own four.  (Rounds 2-4 started this at 8 for "the four
-    // private requests of the prologue" -- but those go out IN FRONT of panel 0, so the first panel of a launch was waited for with
-    // vmcnt(8) while it could be among the eight youngest operations: nothing ordered its arrival before the first reads.  It never
-    // showed with one workgroup per CU -- panel 0 is requested a statistics merge and an operand preparation ahead -- and did within
-    // minutes with two (round 5, the STEPS = 2 form: a handful of first-group tiles wrong, run-to-run different).)
-    int since_w = 0;
-    auto panel_begin = [&](int next) -> int {
-        if (since_w >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else if (STEPS < 4 && since_w >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");   // half panels: two items per panel
-        else if (since_w >= 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const int rd = c.q & 1;
-        glds_quad_s(c.lane16, panel_src(next), c.w_lds + (unsigned)((c.q + 1) & 1) * (PU4 * 16u));
-        since_w = 0;
-        ++c.q;
-        return rd;
-    };
     // sources of the concatenated input by k16-step (stage 1 and the shortcut / residual read the same tensors)
     auto xin = [&](const TilePtrs& t, int S) -> const char* { return SCLIN && S >= 8 ? t.x1 + (size_t)(S - 8) * 2048 : t.x0 + (size_t)S * 2048; };
 
@@ -494,7 +652,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
         const TilePtrs cur = tile_ptrs<SCLIN, PW>(a, g, wave);
         const bool my_cond = cur.cond;
         const TilePtrs nxt = tile_ptrs<SCLIN, PW>(a, g + stride < ngroups ? g + stride : g, wave);
-        DSG_PSTAMP(0x01);
+        w.stamp(0x01);
         // the item four places behind position `T` of the part that follows stage 1: condition embedding (conditional tiles),
         // then the shortcut / residual input, then the next tile's statistics and first steps
         auto issue_tail = [&](int T) {            // T counts from the first shortcut / residual item
@@ -516,7 +674,6 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             issue_tail(S + 4);
             return rd;
         };
-        auto no_consume = [&](int) -> const uint4* { return nullptr; };
 
         // ---- LN1 statistics (Chan merge of the producers' (mean, M2)), as resblock_body_h; `t` = the tile they belong to
         auto ln1_stats = [&](const TilePtrs& t, float& cc, float& dd) {
@@ -536,133 +693,62 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             cc = rstd; dd = -mean * rstd;
         };
 
-        // ---- stage 1: memory-fed, LayerNorm + SiLU.  Step 0's operand is prepared on its own (first tile of the workgroup; every tile
-        // where !XT) or arrives from the previous tile's last panel; every other step under the MFMAs of the step before it.
-        auto step0_mem = [&](const uint4* rd, const float* gv, const float* bv, float cc, float dd) -> BOp {
-            const float4 xa = __builtin_bit_cast(float4, rd[0]), xb = __builtin_bit_cast(float4, rd[64]);
-            const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
-        };
-        auto step0_reg = [&](const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd) -> BOp {
-            const float x[8] = {in[0][0], in[0][1], in[0][2], in[0][3], in[0][4], in[0][5], in[0][6], in[0][7]};
-            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
-        };
-        auto none_n = [&]() -> const uint4* { return nullptr; };
+        // ---- stage 1.  Step 0's operand is prepared on its own (first tile of the workgroup; every tile where !XT) or arrives from the
+        // previous tile's last panel.
         f32x16 acc1[NT];
         {
             float cc, dd;
             BOp b0;
             if (!XT || g == (int)blockIdx.x) {
                 ln1_stats(cur, cc, dd);
-                DSG_PSTAMP(0x10);
-                b0 = step0_mem(consume_s1(0), g1v, b1v, cc, dd);
+                w.stamp(0x10);
+                b0 = w.step0_mem(consume_s1(0), w.g1v, w.b1v, cc, dd);
                 asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
             } else {
                 b0 = bcar; cc = cc_car; dd = dd_car;
             }
-            DSG_PSTAMP(0x11);
-#pragma unroll
-            for (int p = 0; p < P1; ++p) {
-                const int bi = panel_begin(p + 1);
-                DSG_PSTAMP(0x14);
-                BOp bc;
-                const NextPrep nx{&acc1, STEPS * (p + 1), g1v, b1v, cc, dd, nullptr, nullptr};
-                auto cs = [&](int jj) { return consume_s1(STEPS * p + 1 + jj); };
-                auto cn = [&]() { return consume_s1(STEPS * p + STEPS); };
-                if (p + 1 < P1) {
-                    if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
-                    else panel_pipe_s<false, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
-                    b0 = bc;
-                } else {
-                    if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
-                    else panel_pipe_s<false, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
-                }
-                DSG_PSTAMP(0x12);
-            }
+            w.stamp(0x11);
+            w.template stage1<P1>(acc1, b0, cc, dd, consume_s1, [&](int p) { return panel_src(p + 1); });
         }
-        acc_unscale_add_lds<NT>(acc1, inv1, tbv, h);
-        DSG_PSTAMP(0x13);
+        acc_unscale_add_lds<NT>(acc1, inv1, w.tbv, h);
+        w.stamp(0x13);
 
         // ---- stage 2: register-fed
         f32x16 acc2[NT];
         {
-            float mean, m2;
-            acc_stats<N, NT>(acc1, h, mean, m2);
-            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-            DSG_PSTAMP(0x20);
-            BOp b0 = step0_reg(acc1, g2v, b2v, cc, dd), bc;
-            asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
-            DSG_PSTAMP(0x21);
-#pragma unroll
-            for (int p = 0; p < P2; ++p) {           // 8 k16-steps in P2 panels
-                const int bi = panel_begin(PA + p + 1);
-                DSG_PSTAMP(0x24);
-                const NextPrep nx{&acc1, STEPS * (p + 1 < P2 ? p + 1 : 0), g2v, b2v, cc, dd, nullptr, nullptr};
-                if (p + 1 < P2) {
-                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                    else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                    b0 = bc;
-                } else {
-                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_NONE, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                    else panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                }
-                DSG_PSTAMP(0x22);
-            }
-            acc_unscale_add_lds<NT>(acc2, inv2, c2v, h);
+            float cc, dd;
+            BOp b0 = w.template reg_head<0x20>(acc1, w.g2v, w.b2v, cc, dd);
+            w.template reg_panels<P2 - 1, 0x20>(acc2, acc1, w.g2v, w.b2v, cc, dd, b0, [&](int p) { return panel_src(PA + p + 1); });
+            w.template reg_last<0x20>(acc2, acc1, w.g2v, w.b2v, cc, dd, b0, panel_src(PA + P2));
+            acc_unscale_add_lds<NT>(acc2, inv2, w.c2v, h);
         }
-        if (my_cond) {                 // condition embedding of this tile: 8 private items, one accumulator tile per two
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    const int i = 2 * e + hf;
-                    const uint4* rd = priv_consume(c);
-                    const float4 cv0 = __builtin_bit_cast(float4, rd[0]), cv1 = __builtin_bit_cast(float4, rd[64]);
-                    if (i + 4 < 8) { priv_issue(c, cur.cp + (size_t)(i + 4) * 2048); since_w += 2; }
-                    else issue_tail(i + 4 - 8);
-                    const int r0 = 8 * hf;
-                    acc2[e][r0 + 0] += cv0.x; acc2[e][r0 + 1] += cv0.y; acc2[e][r0 + 2] += cv0.z; acc2[e][r0 + 3] += cv0.w;
-                    acc2[e][r0 + 4] += cv1.x; acc2[e][r0 + 5] += cv1.y; acc2[e][r0 + 6] += cv1.z; acc2[e][r0 + 7] += cv1.w;
-                }
-            }
-        }
-        DSG_PSTAMP(0x23);
+        if (my_cond)                   // condition embedding of this tile: 8 private items, one accumulator tile per two
+            w.priv_add8(acc2, [&](int i) {
+                if (i + 4 < 8) { priv_issue(c, cur.cp + (size_t)(i + 4) * 2048); since_w += 2; }
+                else issue_tail(i + 4 - 8);
+            });
+        w.stamp(0x23);
 
         // ---- stage 3 (+ shortcut in the same scaled accumulator).  The shortcut's first operand (raw input, split only) is prepared
         // under the last step of stage 3, the next tile's first operand (XT) under the last step of the shortcut.
         f32x16 (&acc3)[NT] = acc1;
         {
-            float mean, m2;
-            acc_stats<N, NT>(acc2, h, mean, m2);
-            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-            DSG_PSTAMP(0x30);
-            BOp b0 = step0_reg(acc2, g3v, b3v, cc, dd), bc, bsc;
-            asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
-            DSG_PSTAMP(0x31);
-            int bi = 0;
-#pragma unroll
-            for (int p = 0; p + 1 < P2; ++p) {       // every panel of the stage but its last
-                bi = panel_begin(PB + p + 1);
-                DSG_PSTAMP(0x34);
-                const NextPrep nx{&acc2, STEPS * (p + 1), g3v, b3v, cc, dd, nullptr, nullptr};
-                if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
-                else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
-                b0 = bc;
-                DSG_PSTAMP(0x32);
-            }
-            bc = b0;                                 // operand of the stage's last panel
-            constexpr int SL = 8 - STEPS;            // its first k16-step
-            bi = panel_begin((PD) % NP);
-            DSG_PSTAMP(0x34);
+            float cc, dd;
+            BOp b0 = w.template reg_head<0x30>(acc2, w.g3v, w.b3v, cc, dd), bsc;
+            w.template reg_panels<P2 - 1, 0x30>(acc3, acc2, w.g3v, w.b3v, cc, dd, b0, [&](int p) { return panel_src(PB + p + 1); });
             if (SCLIN) {
+                constexpr int SL = 8 - STEPS;            // first k16-step of the stage's last panel
+                int bi = w.panel_begin(panel_src(PD % NP));
+                w.stamp(0x34);
+                const float* const g3v = w.g3v, * const b3v = w.b3v;
                 const NextPrep raw{&acc2, 0, g3v, b3v, 1.f, 0.f, nullptr, nullptr};
-                panel_pipe_s<false, PIPE_REG, PIPE_RAW, STEPS>(acc3, c.wrd + bi * PU4, bc, bsc, acc2, SL, g3v, b3v, cc, dd, h, no_consume, raw,
+                panel_pipe_s<false, PIPE_REG, PIPE_RAW, STEPS>(acc3, c.wrd + bi * PU4, b0, bsc, acc2, SL, g3v, b3v, cc, dd, h, w.no_consume, raw,
                                                                [&]() { return consume_sc(0); });
-                DSG_PSTAMP(0x32);
+                w.stamp(0x32);
 #pragma unroll
                 for (int p = 0; p < P1; ++p) {
-                    bi = panel_begin((PD + p + 1) % NP);
-                    DSG_PSTAMP(0x44);
+                    bi = w.panel_begin(panel_src((PD + p + 1) % NP));
+                    w.stamp(0x44);
                     BOp bn;
                     auto cs = [&](int jj) { return consume_sc(STEPS * p + 1 + jj); };
                     if (p + 1 < P1) {
@@ -672,7 +758,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
                     } else if (XT) {
                         // the coming tile (the same one again behind the workgroup's last group: its requests are in flight either way): its
                         // row statistics, then its first stage-1 operand under this panel's last step
-                        const NextPrep nt1{&acc3, 0, g1v, b1v, 0.f, 0.f, &cc_car, &dd_car};
+                        const NextPrep nt1{&acc3, 0, w.g1v, w.b1v, 0.f, 0.f, &cc_car, &dd_car};
                         panel_pipe_s<false, PIPE_RAW, PIPE_LN, STEPS>(acc3, c.wrd + bi * PU4, bsc, bcar, acc3, STEPS * p, g3v, b3v, 1.f, 0.f, h, cs, nt1, [&]() {
                             ln1_stats(nxt, cc_car, dd_car);
                             const uint4* rd = priv_consume(c);
@@ -680,44 +766,23 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
                             return rd;
                         });
                     } else {
-                        panel_pipe_s<false, PIPE_RAW, PIPE_NONE, STEPS>(acc3, c.wrd + bi * PU4, bsc, bn, acc3, STEPS * p, g3v, b3v, 1.f, 0.f, h, cs, raw, none_n);
+                        panel_pipe_s<false, PIPE_RAW, PIPE_NONE, STEPS>(acc3, c.wrd + bi * PU4, bsc, bn, acc3, STEPS * p, g3v, b3v, 1.f, 0.f, h, cs, raw, w.none_n);
                     }
-                    DSG_PSTAMP(0x42);
+                    w.stamp(0x42);
                 }
-                acc_unscale_add_lds<NT>(acc3, inv3, c3v, h);
+                acc_unscale_add_lds<NT>(acc3, inv3, w.c3v, h);
             } else {
-                panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc3, c.wrd + bi * PU4, bc, bsc, acc2, SL, g3v, b3v, cc, dd, h, no_consume,
-                                                                NextPrep{&acc2, 0, g3v, b3v, cc, dd, nullptr, nullptr}, none_n);
-                DSG_PSTAMP(0x32);
-                acc_unscale_add_lds<NT>(acc3, inv3, c3v, h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) {
-                        const int i = 2 * e + hf;
-                        const uint4* rd = priv_consume(c);
-                        const float4 xv0 = __builtin_bit_cast(float4, rd[0]), xv1 = __builtin_bit_cast(float4, rd[64]);
-                        issue_tail(i + 4);
-                        const int r0 = 8 * hf;
-                        acc3[e][r0 + 0] += xv0.x; acc3[e][r0 + 1] += xv0.y; acc3[e][r0 + 2] += xv0.z; acc3[e][r0 + 3] += xv0.w;
-                        acc3[e][r0 + 4] += xv1.x; acc3[e][r0 + 5] += xv1.y; acc3[e][r0 + 6] += xv1.z; acc3[e][r0 + 7] += xv1.w;
-                    }
-                }
+                w.template reg_last<0x30>(acc3, acc2, w.g3v, w.b3v, cc, dd, b0, panel_src(PD % NP));
+                acc_unscale_add_lds<NT>(acc3, inv3, w.c3v, h);
+                w.priv_add8(acc3, [&](int i) { issue_tail(i + 4); });       // the residual re-read
             }
         }
-        DSG_PSTAMP(0x43);
+        w.stamp(0x43);
 
         // ---- statistics + store
         float xmean, xm2;
-        acc_stats<N, NT>(acc3, h, xmean, xm2);
-        if ((EPI == 0 || A.store_block_out) && live) {
-            if (h == 0) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + j] = make_float2(xmean, xm2);
-#pragma unroll
-            for (int G = 0; G < NG; ++G)
-                st4(a.out + ((size_t)tile * NG + G) * 256 + lane * 4,
-                    make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]));
-        }
-        DSG_PSTAMP(0x50);
+        w.stats_store(acc3, a, tile, (EPI == 0 || A.store_block_out) && live, xmean, xm2);
+        w.stamp(0x50);
         if (EPI == 0) continue;
         if (EPI == 1) range_check(a.range_flag, xmean, xm2);
 
@@ -729,16 +794,16 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             const uint4* pn = nullptr;
 #pragma unroll
             for (int S = 0; S < 8; ++S) {
-                if (S % ESTEPS == 0) pn = c.wrd + panel_begin((PE + S / ESTEPS + 1) % NP) * PU4;
+                if (S % ESTEPS == 0) pn = c.wrd + w.panel_begin(panel_src((PE + S / ESTEPS + 1) % NP)) * PU4;
                 const int sl = S % ESTEPS, t = S >> 1, r0 = 8 * (S & 1);
-                HFrag<NTO> w;
-                panel_wfrag<NTO>(w, pn, ESTEPS, sl);
+                HFrag<NTO> wf;
+                panel_wfrag<NTO>(wf, pn, ESTEPS, sl);
                 const float x[8] = {acc3[t][r0], acc3[t][r0 + 1], acc3[t][r0 + 2], acc3[t][r0 + 3], acc3[t][r0 + 4], acc3[t][r0 + 5], acc3[t][r0 + 6],
                                     acc3[t][r0 + 7]};
                 float v[8];
                 if (EPI == 2) {
-                    const float4 g0 = ld4(gLv + 16 * S + 4 * h), b0 = ld4(bLv + 16 * S + 4 * h);
-                    const float4 g1 = ld4(gLv + 16 * S + 8 + 4 * h), b1 = ld4(bLv + 16 * S + 8 + 4 * h);
+                    const float4 g0 = ld4(w.gLv + 16 * S + 4 * h), b0 = ld4(w.bLv + 16 * S + 4 * h);
+                    const float4 g1 = ld4(w.gLv + 16 * S + 8 + 4 * h), b1 = ld4(w.bLv + 16 * S + 8 + 4 * h);
                     act8_l2(v, x, cc, dd, g0, b0, g1, b1);
                 } else {
 #pragma unroll
@@ -746,10 +811,10 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
                 }
                 h8 bhi, blo;
                 split8(v, bhi, blo);
-                if (S == 0) mfma_step_h0<NTO>(acc, w, bhi, blo); else mfma_step_h<NTO>(acc, w, bhi, blo);
+                if (S == 0) mfma_step_h0<NTO>(acc, wf, bhi, blo); else mfma_step_h<NTO>(acc, wf, bhi, blo);
             }
         }
-        acc_unscale_add_lds<NTO>(acc, invL, biasLv, h);
+        acc_unscale_add_lds<NTO>(acc, invL, w.biasLv, h);
         if (!live) continue;
         if (EPI == 1) {
             const int NGo = (la.out_width + 7) / 8;
@@ -758,9 +823,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             if (h == 0) reinterpret_cast<float2*>(la.out_stats)[(size_t)tile * 32 + j] = make_float2(m, sq);
 #pragma unroll
             for (int G = 0; G < NTO * 4; ++G)
-                if (G < NGo)
-                    st4(la.out + ((size_t)tile * NGo + G) * 256 + lane * 4,
-                        make_float4(acc[G >> 2][4 * (G & 3)], acc[G >> 2][4 * (G & 3) + 1], acc[G >> 2][4 * (G & 3) + 2], acc[G >> 2][4 * (G & 3) + 3]));
+                if (G < NGo) st4(la.out + ((size_t)tile * NGo + G) * 256 + lane * 4, acc_f4<NTO>(acc, G));
         } else {
             const int pass = tile >= la.tiles_per_pass ? 1 : 0, row = ptile * 32 + j;
             if (row < la.nrows) {
@@ -769,8 +832,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
 #pragma unroll
                     for (int G = 0; G < NTO * 4; ++G) {
                         const int f = 8 * G + 4 * h;
-                        if (f < la.out_width)
-                            st4(o + f, make_float4(acc[G >> 2][4 * (G & 3)], acc[G >> 2][4 * (G & 3) + 1], acc[G >> 2][4 * (G & 3) + 2], acc[G >> 2][4 * (G & 3) + 3]));
+                        if (f < la.out_width) st4(o + f, acc_f4<NTO>(acc, G));
                     }
                 } else {
 #pragma unroll
@@ -784,18 +846,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stream's last requests are redundant: nothing may land in LDS after the end
-#ifdef DSG_CYCLE_STAMPS
-    if (STAMPED && blockIdx.x == 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < 128; k += 64) dsg_stamp_buf[wave * 128 + k] = k < stamp_k ? stamp_lds[wave * 128 + k] : 0ull;
-        if (threadIdx.x == 0) {
-            dsg_stamp_buf[kPW * 128 + 0] = clk_t0; dsg_stamp_buf[kPW * 128 + 1] = clk_r0;
-            dsg_stamp_buf[kPW * 128 + 2] = __builtin_readcyclecounter(); dsg_stamp_buf[kPW * 128 + 3] = __builtin_amdgcn_s_memrealtime();
-            dsg_stamp_n = kPW * 128 + 4;
-        }
-    }
-#endif
+    w.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -810,49 +861,28 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
 //     acc2 += cond_emb
 //     stage 3 from acc2, + c3, + x, statistics      -> store tile tiles_per_pass + ptile
 // Stage 3 only READS acc2 (its accumulators alias acc1), so nothing new is live; the residual input is read twice from the private
-// stream rather than held.  Every piece (panel_pipe_s, panel_prep, acc_unscale_add_lds, acc_stats) is the one k_panel128_h runs, in
-// the same order per output tile: the result is bit-identical.
+// stream rather than held.  Every piece is the PanelWg member k_panel128_h runs, in the same order per output tile: the result is
+// bit-identical.
 // Weight-panel program per row tile: P panels of W1, P of W2, P of W3, P of W3 again (P = 8 / STEPS), then the next group's W1.
 // Private stream per row tile: [statistics | 8 x (stage 1) | 8 x (residual) | 8 cond_emb | 8 x (residual) | next group's statistics
 // and first three x items]: 33 items where the two tiles took 42.
 template <int STEPS = 4>
 __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(const BlockArgsH ah, const int ngroups) {
-    constexpr int N = 128, NT = 4, NG = 16;
-    constexpr int PW = panel_pw(STEPS), PU4 = panel_u4(STEPS), NTHR = 64 * PW;
+    constexpr int NT = 4;
+    constexpr int PW = panel_pw(STEPS);
     constexpr int P = 8 / STEPS;                               // panels per stage (8 k16-steps each)
     constexpr int PA = P, PB = 2 * P, PD = 3 * P, NP = 4 * P;  // W2 / W3 / W3 again start here; panels per row tile
     __shared__ uint4 lds[panel_lds_u4(STEPS) + (STEPS == 4 ? kPanelStampU4 : 0)];
-#ifdef DSG_CYCLE_STAMPS
-    unsigned long long* const stamp_lds = reinterpret_cast<unsigned long long*>(lds + panel_lds_u4(STEPS));
-    int stamp_k = 0;
-    constexpr bool STAMPED = DSG_STAMP_DOWN0 && STEPS == 4;
-    const unsigned long long clk_t0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    float* const vec = reinterpret_cast<float*>(lds + 2 * PU4 + PW * kPrivSlots * kPrivU4);
-    float* const g1v = vec, * const b1v = vec + kLnLdsW1, * const v2 = vec + 2 * kLnLdsW1;
-    float* const g2v = v2, * const b2v = v2 + 128, * const g3v = v2 + 256, * const b3v = v2 + 384, * const tbv = v2 + 512, * const c2v = v2 + 640,
-         * const c3v = v2 + 768;
+    PanelWg<STEPS, (DSG_STAMP_DOWN0 && STEPS == 4)> w;
+    w.init(lds);
+    PanelCtx& c = w.c;
+    int& since_w = w.since_w;
     const BlockArgs& a = ah.b;
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = w.lane, h = w.h, j = w.j, wave = w.wave;
     const int stride = gridDim.x;
     const int tpp = a.tiles_per_pass;
-    if (STEPS == 4 && wave >= 4) __builtin_amdgcn_s_setprio(DSG_PANEL_TRAIL_PRIO);      // as k_panel128_h: the younger wave of a SIMD
-    constexpr float kL2 = -1.44269504088896341f;
-
-    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e)
-    {
-        const int n1 = ln1_extent(a);
-        for (int i = threadIdx.x; i < n1; i += NTHR) { g1v[i] = a.gamma1[i] * kL2; b1v[i] = a.beta1[i] * kL2; }
-        if (threadIdx.x < 128) {
-            const int i = threadIdx.x;
-            g2v[i] = a.gamma2[i] * kL2; b2v[i] = a.beta2[i] * kL2; g3v[i] = a.gamma3[i] * kL2; b3v[i] = a.beta3[i] * kL2;
-            c2v[i] = a.c2[i]; c3v[i] = a.c3[i];
-            tbv[i] = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + i];
-        }
-    }
+    w.stage_vectors(a, [](int) {});
     const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
-    __syncthreads();                   // no DMA is in flight yet: a plain barrier
 
     // ---- this wave's 4 KiB of every weight panel: (out tile, two of its STEPS k16-steps)
     const int wnt = wave / (STEPS / 2), wsub = wave % (STEPS / 2);
@@ -874,42 +904,10 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
         return RowPtrs{reinterpret_cast<const char*>(a.in0.data + (size_t)pt * 16 * 256), reinterpret_cast<const char*>(a.in0.stats + (size_t)pt * 64),
                        reinterpret_cast<const char*>(a.cond_pre + (size_t)pt * 16 * 256)};
     };
-
-    const unsigned lds0 = (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void*)lds;
-    PanelCtx c;
-    c.lane16 = (unsigned)lane * 16u; c.lane4 = (unsigned)lane * 4u;
-    c.w_lds = lds0 + (unsigned)wave * 4096u;
-    c.w_rd = lds0 + (unsigned)lane * 16u;
-    c.p_lds = lds0 + 2u * PU4 * 16u + (unsigned)wave * (kPrivSlots * 2048u);
-    c.wrd = lds + lane;
-    c.prd = lds + 2 * PU4 + wave * (kPrivSlots * kPrivU4) + lane;
-    c.q = 0; c.islot = 0; c.cslot = 0;
-
-    // prologue: the first four private items of this wave's first row tile, then panel 0 into buffer 0
     {
         const RowPtrs cur = row_ptrs(blockIdx.x < ngroups ? blockIdx.x : 0);
-        priv_issue_stats(c, cur.st0, cur.st0);
-        priv_issue(c, cur.x0);
-        priv_issue(c, cur.x0 + 2048);
-        priv_issue(c, cur.x0 + 4096);
+        w.prologue(cur.st0, cur.st0, cur.x0, panel_src(0));
     }
-    glds_quad_s(c.lane16, panel_src(0), c.w_lds);
-
-    // One barrier per panel, as k_panel128_h.  `since_w`: DMA operations of the private stream issued BEHIND the pending panel's own
-    // four; 0 at the start (the prologue's requests went out IN FRONT of panel 0, so the launch's first panel is waited for with vmcnt(0)).
-    int since_w = 0;
-    auto panel_begin = [&](int next) -> int {
-        if (since_w >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else if (STEPS < 4 && since_w >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else if (since_w >= 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const int rd = c.q & 1;
-        glds_quad_s(c.lane16, panel_src(next), c.w_lds + (unsigned)((c.q + 1) & 1) * (PU4 * 16u));
-        since_w = 0;
-        ++c.q;
-        return rd;
-    };
 
     for (int g = blockIdx.x; g < ngroups; g += stride) {
         const int row_raw = g * PW + wave;
@@ -917,7 +915,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
         const int ptile = live ? row_raw : tpp - 1;
         const RowPtrs cur = row_ptrs(g);
         const RowPtrs nxt = row_ptrs(g + stride < ngroups ? g + stride : g);
-        DSG_PSTAMP(0x01);
+        w.stamp(0x01);
         // the item at position T of the part of the stream that follows stage 1 (T is a compile-time constant at every call site)
         auto issue_at = [&](int T) {
             if (T < 8) priv_issue(c, cur.x0 + (size_t)T * 2048);                        // residual read, unconditional pass
@@ -934,17 +932,6 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
             else issue_at(S + 4 - 8);
             return rd;
         };
-        auto no_consume = [&](int) -> const uint4* { return nullptr; };
-        auto none_n = [&]() -> const uint4* { return nullptr; };
-        auto step0_mem = [&](const uint4* rd, const float* gv, const float* bv, float cc, float dd) -> BOp {
-            const float4 xa = __builtin_bit_cast(float4, rd[0]), xb = __builtin_bit_cast(float4, rd[64]);
-            const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
-        };
-        auto step0_reg = [&](const f32x16 (&in)[NT], const float* gv, const float* bv, float cc, float dd) -> BOp {
-            const float x[8] = {in[0][0], in[0][1], in[0][2], in[0][3], in[0][4], in[0][5], in[0][6], in[0][7]};
-            return panel_prep<true, true>(x, gv, bv, 0, cc, dd, h);
-        };
 
         // ---- stage 1 (memory-fed), once for both passes
         f32x16 acc1[NT];
@@ -957,58 +944,25 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
                 const float rstd = rsqrtf(s0.y * a.inv_nin + kLnEps);
                 cc = rstd; dd = -s0.x * rstd;
             }
-            DSG_PSTAMP(0x10);
-            BOp b0 = step0_mem(consume_s1(0), g1v, b1v, cc, dd);
+            w.stamp(0x10);
+            BOp b0 = w.step0_mem(consume_s1(0), w.g1v, w.b1v, cc, dd);
             asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
-            DSG_PSTAMP(0x11);
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                const int bi = panel_begin(p + 1);
-                DSG_PSTAMP(0x14);
-                BOp bc;
-                const NextPrep nx{&acc1, STEPS * (p + 1), g1v, b1v, cc, dd, nullptr, nullptr};
-                auto cs = [&](int jj) { return consume_s1(STEPS * p + 1 + jj); };
-                auto cn = [&]() { return consume_s1(STEPS * p + STEPS); };
-                if (p + 1 < P) {
-                    if (p == 0) panel_pipe_s<true, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
-                    else panel_pipe_s<false, PIPE_LN, PIPE_LN, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, cn);
-                    b0 = bc;
-                } else {
-                    panel_pipe_s<false, PIPE_LN, PIPE_NONE, STEPS>(acc1, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g1v, b1v, cc, dd, h, cs, nx, none_n);
-                }
-                DSG_PSTAMP(0x12);
-            }
+            w.stamp(0x11);
+            w.template stage1<P>(acc1, b0, cc, dd, consume_s1, [&](int p) { return panel_src(p + 1); });
         }
-        acc_unscale_add_lds<NT>(acc1, inv1, tbv, h);
-        DSG_PSTAMP(0x13);
+        acc_unscale_add_lds<NT>(acc1, inv1, w.tbv, h);
+        w.stamp(0x13);
 
         // ---- stage 2 (register-fed), once for both passes
         f32x16 acc2[NT];
         {
-            float mean, m2;
-            acc_stats<N, NT>(acc1, h, mean, m2);
-            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-            DSG_PSTAMP(0x20);
-            BOp b0 = step0_reg(acc1, g2v, b2v, cc, dd), bc;
-            asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
-            DSG_PSTAMP(0x21);
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                const int bi = panel_begin(PA + p + 1);
-                DSG_PSTAMP(0x24);
-                const NextPrep nx{&acc1, STEPS * (p + 1 < P ? p + 1 : 0), g2v, b2v, cc, dd, nullptr, nullptr};
-                if (p + 1 < P) {
-                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                    else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                    b0 = bc;
-                } else {
-                    panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc2, c.wrd + bi * PU4, b0, bc, acc1, STEPS * p, g2v, b2v, cc, dd, h, no_consume, nx, none_n);
-                }
-                DSG_PSTAMP(0x22);
-            }
-            acc_unscale_add_lds<NT>(acc2, inv2, c2v, h);
+            float cc, dd;
+            BOp b0 = w.template reg_head<0x20>(acc1, w.g2v, w.b2v, cc, dd);
+            w.template reg_panels<P - 1, 0x20>(acc2, acc1, w.g2v, w.b2v, cc, dd, b0, [&](int p) { return panel_src(PA + p + 1); });
+            w.template reg_last<0x20>(acc2, acc1, w.g2v, w.b2v, cc, dd, b0, panel_src(PA + P));
+            acc_unscale_add_lds<NT>(acc2, inv2, w.c2v, h);
         }
-        DSG_PSTAMP(0x23);
+        w.stamp(0x23);
 
         // ---- per pass: (+ condition embedding,) stage 3 from acc2, residual add, statistics, store
         f32x16 (&acc3)[NT] = acc1;
@@ -1017,89 +971,26 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
             const int pbase = pass == 0 ? PB : PD;       // this pass's W3 panels
             const int tbase = pass == 0 ? 0 : 16;        // stream position of this pass's residual items
             if (pass == 1) {           // condition embedding of the row tile: 8 private items, one accumulator tile per two
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) {
-                        const int i = 2 * e + hf;
-                        const uint4* rd = priv_consume(c);
-                        const float4 cv0 = __builtin_bit_cast(float4, rd[0]), cv1 = __builtin_bit_cast(float4, rd[64]);
-                        issue_at(8 + i + 4);
-                        const int r0 = 8 * hf;
-                        acc2[e][r0 + 0] += cv0.x; acc2[e][r0 + 1] += cv0.y; acc2[e][r0 + 2] += cv0.z; acc2[e][r0 + 3] += cv0.w;
-                        acc2[e][r0 + 4] += cv1.x; acc2[e][r0 + 5] += cv1.y; acc2[e][r0 + 6] += cv1.z; acc2[e][r0 + 7] += cv1.w;
-                    }
-                }
-                DSG_PSTAMP(0x33);
+                w.priv_add8(acc2, [&](int i) { issue_at(8 + i + 4); });
+                w.stamp(0x33);
             }
             {
-                float mean, m2;
-                acc_stats<N, NT>(acc2, h, mean, m2);
-                const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-                DSG_PSTAMP(0x30);
-                BOp b0 = step0_reg(acc2, g3v, b3v, cc, dd), bc, bsc;
-                asm volatile("" : "+v"(b0.hi), "+v"(b0.lo));
-                DSG_PSTAMP(0x31);
-                int bi = 0;
-#pragma unroll
-                for (int p = 0; p + 1 < P; ++p) {        // every panel of the stage but its last
-                    bi = panel_begin(pbase + p + 1);
-                    DSG_PSTAMP(0x34);
-                    const NextPrep nx{&acc2, STEPS * (p + 1), g3v, b3v, cc, dd, nullptr, nullptr};
-                    if (p == 0) panel_pipe_s<true, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
-                    else panel_pipe_s<false, PIPE_REG, PIPE_REG, STEPS>(acc3, c.wrd + bi * PU4, b0, bc, acc2, STEPS * p, g3v, b3v, cc, dd, h, no_consume, nx, none_n);
-                    b0 = bc;
-                    DSG_PSTAMP(0x32);
-                }
-                bc = b0;                                 // operand of the stage's last panel
-                constexpr int SL = 8 - STEPS;            // its first k16-step
-                bi = panel_begin((pbase + P) % NP);      // behind the second pass: the next group's first W1 panel
-                DSG_PSTAMP(0x34);
-                panel_pipe_s<false, PIPE_REG, PIPE_NONE, STEPS>(acc3, c.wrd + bi * PU4, bc, bsc, acc2, SL, g3v, b3v, cc, dd, h, no_consume,
-                                                                NextPrep{&acc2, 0, g3v, b3v, cc, dd, nullptr, nullptr}, none_n);
-                DSG_PSTAMP(0x32);
-                acc_unscale_add_lds<NT>(acc3, inv3, c3v, h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) {
-                        const int i = 2 * e + hf;
-                        const uint4* rd = priv_consume(c);
-                        const float4 xv0 = __builtin_bit_cast(float4, rd[0]), xv1 = __builtin_bit_cast(float4, rd[64]);
-                        issue_at(tbase + i + 4);
-                        const int r0 = 8 * hf;
-                        acc3[e][r0 + 0] += xv0.x; acc3[e][r0 + 1] += xv0.y; acc3[e][r0 + 2] += xv0.z; acc3[e][r0 + 3] += xv0.w;
-                        acc3[e][r0 + 4] += xv1.x; acc3[e][r0 + 5] += xv1.y; acc3[e][r0 + 6] += xv1.z; acc3[e][r0 + 7] += xv1.w;
-                    }
-                }
+                float cc, dd;
+                BOp b0 = w.template reg_head<0x30>(acc2, w.g3v, w.b3v, cc, dd);
+                w.template reg_panels<P - 1, 0x30>(acc3, acc2, w.g3v, w.b3v, cc, dd, b0, [&](int p) { return panel_src(pbase + p + 1); });
+                // behind the second pass: the next group's first W1 panel
+                w.template reg_last<0x30>(acc3, acc2, w.g3v, w.b3v, cc, dd, b0, panel_src((pbase + P) % NP));
+                acc_unscale_add_lds<NT>(acc3, inv3, w.c3v, h);
+                w.priv_add8(acc3, [&](int i) { issue_at(tbase + i + 4); });       // the residual re-read
             }
-            DSG_PSTAMP(0x43);
+            w.stamp(0x43);
             // ---- statistics + store: tile `ptile` of the unconditional pass, `tiles_per_pass + ptile` of the conditional one
             float xmean, xm2;
-            acc_stats<N, NT>(acc3, h, xmean, xm2);
-            if (live) {
-                const int tile = pass == 0 ? ptile : tpp + ptile;
-                if (h == 0) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + j] = make_float2(xmean, xm2);
-#pragma unroll
-                for (int G = 0; G < NG; ++G)
-                    st4(a.out + ((size_t)tile * NG + G) * 256 + lane * 4,
-                        make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]));
-            }
-            DSG_PSTAMP(0x50);
+            w.stats_store(acc3, a, pass == 0 ? ptile : tpp + ptile, live, xmean, xm2);
+            w.stamp(0x50);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stream's last requests are redundant: nothing may land in LDS after the end
-#ifdef DSG_CYCLE_STAMPS
-    if (STAMPED && blockIdx.x == 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int k = lane; k < 128; k += 64) dsg_stamp_buf[wave * 128 + k] = k < stamp_k ? stamp_lds[wave * 128 + k] : 0ull;
-        if (threadIdx.x == 0) {
-            dsg_stamp_buf[kPW * 128 + 0] = clk_t0; dsg_stamp_buf[kPW * 128 + 1] = clk_r0;
-            dsg_stamp_buf[kPW * 128 + 2] = __builtin_readcyclecounter(); dsg_stamp_buf[kPW * 128 + 3] = __builtin_amdgcn_s_memrealtime();
-            dsg_stamp_n = kPW * 128 + 4;
-        }
-    }
-#endif
+    w.finish();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -145,6 +145,175 @@ struct R64Tile {                // where a row tile's operands live
     const float2 *st0, *st1;    // row statistics (+ j)
     bool cond;
 };
+template <bool SCLIN>
+__device__ __forceinline__ R64Tile r64_tile(const BlockArgs& a, int g, int wave, int lane, int j) {
+    const int traw = g * kR64Waves + wave;
+    const int tile = traw < a.ntiles ? traw : a.ntiles - 1;
+    const int ptile = tile >= a.tiles_per_pass ? tile - a.tiles_per_pass : tile;
+    const int t0 = seg_tile(a.in0, tile), t1 = seg_tile(a.in1, tile);
+    R64Tile t;
+    t.x0 = a.in0.data + (size_t)t0 * 8 * 256 + lane * 4;
+    t.st0 = reinterpret_cast<const float2*>(a.in0.stats) + (size_t)t0 * 32 + j;
+    t.x1 = SCLIN ? a.in1.data + (size_t)t1 * 8 * 256 + lane * 4 : t.x0;
+    t.st1 = SCLIN ? reinterpret_cast<const float2*>(a.in1.stats) + (size_t)t1 * 32 + j : t.st0;
+    t.cp = a.cond_pre + (size_t)ptile * 8 * 256 + lane * 4;
+    t.cond = tile >= a.uncond_tiles;
+    return t;
+}
+
+// ---- a block's planes and vectors -> LDS, once per launch, in two phases: r64_staged_load issues EVERY global load into registers,
+// r64_staged_write writes them to the LDS image at `lb`.  A kernel calls all its loads before its first write: written as
+// `for (i...) lds[i] = src[i]` hipcc emits load -> s_waitcnt vmcnt(0) -> ds_write per iteration, 13 dependent L2 round trips (1 us of
+// the 5-6 us every launch costs before its first tile: profiles/r03d_fixed_cost.txt)
+template <bool SCLIN, int NTO>
+struct R64Staged {
+    static constexpr int KS1 = R64Layout<SCLIN, NTO>::KS1, N1 = 2 * KS1 * 128 / 512, N2 = 2 * 4 * 128 / 512, NL = (NTO * 4 * 128 + 511) / 512;
+    uint4 r1[N1], r2[N2], r3[N2], rs[SCLIN ? N1 : 1], rl[NTO > 0 ? NL : 1];
+    float g1, b1, bl, v6[6], tb;
+};
+template <bool SCLIN, int NTO>
+__device__ __forceinline__ void r64_staged_load(R64Staged<SCLIN, NTO>& s, const BlockArgsH& ah, const LinArgsH* lin /* NTO > 0 */, int tid) {
+    using S = R64Staged<SCLIN, NTO>;
+    const BlockArgs& a = ah.b;
+    s.g1 = 0.f; s.b1 = 0.f; s.bl = 0.f; s.tb = 0.f;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s.v6[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < S::N1; ++k) s.r1[k] = ah.W1h[tid + 512 * k];
+#pragma unroll
+    for (int k = 0; k < S::N2; ++k) { s.r2[k] = ah.W2h[tid + 512 * k]; s.r3[k] = ah.W3h[tid + 512 * k]; }
+    if constexpr (SCLIN) {
+#pragma unroll
+        for (int k = 0; k < S::N1; ++k) s.rs[k] = ah.Wsch[tid + 512 * k];
+    }
+    if constexpr (NTO > 0) {
+#pragma unroll
+        for (int k = 0; k < S::NL; ++k) {           // (whole 512-piece rounds unconditionally: a conditionally written array element sends
+            s.rl[k] = make_uint4(0u, 0u, 0u, 0u);   // the array to scratch memory)
+            if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) s.rl[k] = lin->Wh[tid + 512 * k];
+        }
+        if (tid < 32 * NTO) s.bl = lin->l.bias[tid];
+    }
+    if (tid < 16 * S::KS1) { s.g1 = a.gamma1[tid]; s.b1 = a.beta1[tid]; }
+    if (tid < 64) {
+        s.v6[0] = a.gamma2[tid]; s.v6[1] = a.beta2[tid]; s.v6[2] = a.gamma3[tid]; s.v6[3] = a.beta3[tid]; s.v6[4] = a.c2[tid]; s.v6[5] = a.c3[tid];
+        s.tb = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + tid];
+    }
+}
+template <bool SCLIN, int NTO>
+__device__ __forceinline__ void r64_staged_write(const R64Staged<SCLIN, NTO>& s, uint4* lb, int tid) {
+    using S = R64Staged<SCLIN, NTO>;
+    using L = R64Layout<SCLIN, NTO>;
+    constexpr float kL2 = -1.44269504088896341f;
+    float* const vec = reinterpret_cast<float*>(lb + L::VEC);
+#pragma unroll
+    for (int k = 0; k < S::N1; ++k) lb[L::W1 + tid + 512 * k] = s.r1[k];
+#pragma unroll
+    for (int k = 0; k < S::N2; ++k) { lb[L::W2 + tid + 512 * k] = s.r2[k]; lb[L::W3 + tid + 512 * k] = s.r3[k]; }
+    if constexpr (SCLIN) {
+#pragma unroll
+        for (int k = 0; k < S::N1; ++k) lb[L::WSC + tid + 512 * k] = s.rs[k];
+    }
+    if constexpr (NTO > 0) {
+#pragma unroll
+        for (int k = 0; k < S::NL; ++k)
+            if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) lb[L::WL + tid + 512 * k] = s.rl[k];
+        if (tid < 32 * NTO) vec[L::BL + tid] = s.bl;
+    }
+    if (tid < 16 * S::KS1) { vec[L::G1 + tid] = s.g1 * kL2; vec[L::B1 + tid] = s.b1 * kL2; }
+    if (tid < 64) {
+        vec[L::G2 + tid] = s.v6[0] * kL2; vec[L::B2 + tid] = s.v6[1] * kL2; vec[L::G3 + tid] = s.v6[2] * kL2; vec[L::B3 + tid] = s.v6[3] * kL2;
+        vec[L::C2 + tid] = s.v6[4]; vec[L::C3 + tid] = s.v6[5];
+        vec[L::TB + tid] = s.tb;
+    }
+}
+
+// ---- the block program of one row tile, in pieces.  The eight input values of k16-step S: from a tile in fragment registers (two
+// float4 per step), from the accumulators of the stage before
+template <int XG>
+__device__ __forceinline__ auto r64_x_regs(const float4 (&xc)[XG]) {
+    return [&xc](int S, float (&x)[8]) {
+        x[0] = xc[2 * S].x; x[1] = xc[2 * S].y; x[2] = xc[2 * S].z; x[3] = xc[2 * S].w;
+        x[4] = xc[2 * S + 1].x; x[5] = xc[2 * S + 1].y; x[6] = xc[2 * S + 1].z; x[7] = xc[2 * S + 1].w;
+    };
+}
+__device__ __forceinline__ auto r64_x_acc(const f32x16 (&in)[2]) {
+    return [&in](int S, float (&x)[8]) {
+        const int t = S >> 1, r0 = 8 * (S & 1);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = in[t][r0 + q];
+    };
+}
+
+// stage 1 -> + time bias -> stage 2 -> + c2 -> (+ condition embedding) -> stage 3 (still scaled) of the block whose LDS image is at
+// `lb` (layout L), on the input tile `xc` with LN1 statistics (mean1, rstd1).  Every 64-wide form shares this much.
+template <typename L, int XG>
+__device__ __forceinline__ void r64_stages(f32x16 (&acc3)[2], const float4 (&xc)[XG], float mean1, float rstd1, uint4* lb, float inv1, float inv2,
+                                           bool cond, const float* cp, int lane, int h) {
+    constexpr int N = 64, NT = 2, NG = 8, KS1 = L::KS1;
+    lds_cu4* const w1 = (lds_cu4*)(lb + L::W1) + lane;
+    lds_cu4* const w2 = (lds_cu4*)(lb + L::W2) + lane;
+    lds_cu4* const w3 = (lds_cu4*)(lb + L::W3) + lane;
+    const float* const vec = reinterpret_cast<const float*>(lb + L::VEC);
+    // condition embedding of this tile: requested now, added after stage 2
+    float4 cpv[NG];
+    if (cond) {
+#pragma unroll
+        for (int G = 0; G < NG; ++G) cpv[G] = ld4(cp + (size_t)G * 256);
+    }
+    f32x16 (&acc1)[NT] = acc3;
+    r64_stage<true, true, KS1>(acc1, w1, KS1 * 128, vec + L::G1, vec + L::B1, rstd1, -mean1 * rstd1, h, r64_x_regs<XG>(xc), [](int) {});
+    r64_unscale_add<8>(acc1, inv1, vec + L::TB, h);
+    f32x16 acc2[NT];
+    {
+        float mean, m2;
+        acc_stats<N, NT>(acc1, h, mean, m2);
+        const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps);
+        r64_stage<true, true, 4>(acc2, w2, 4 * 128, vec + L::G2, vec + L::B2, rstd, -mean * rstd, h, r64_x_acc(acc1), [](int) {});
+        r64_unscale_add<8>(acc2, inv2, vec + L::C2, h);
+    }
+    if (cond) {
+#pragma unroll
+        for (int G = 0; G < NG; ++G) acc_add_f4<NT>(acc2, G, cpv[G]);
+    }
+    {
+        float mean, m2;
+        acc_stats<N, NT>(acc2, h, mean, m2);
+        const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps);
+        r64_stage<true, true, 4>(acc3, w3, 4 * 128, vec + L::G3, vec + L::B3, rstd, -mean * rstd, h, r64_x_acc(acc2), [](int) {});
+    }
+}
+
+// the lane index as an opaque value for the store sites: hipcc otherwise forms the per-lane 64-bit output addresses in the prologue,
+// keeps them live across the whole tile loop and spills them in the 256-register variants
+__device__ __forceinline__ int r64_opaque_lane(int lane) {
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+// row statistics of a finished tile and, where `store`, both to memory as tile `tile` of the block's output
+__device__ __forceinline__ void r64_stats_store(const f32x16 (&acc)[2], const BlockArgs& a, int tile, bool store, int lane_o, int h, float& xmean,
+                                                float& xm2) {
+    acc_stats<64, 2>(acc, h, xmean, xm2);
+    if (store) {
+        if (lane_o < 32) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + lane_o] = make_float2(xmean, xm2);
+        acc_store<8, 2>(acc, a.out + (size_t)tile * 8 * 256 + lane_o * 4);
+    }
+}
+
+// A block WITHOUT Linear shortcut, given its input tile in registers (`xc`, statistics `sc`) and its image in LDS:
+// r64_stages -> + c3 -> + x (the residual, from the same registers stage 1 read) -> statistics -> store.
+// next_input(): the caller's requests for the tile it works on next, issued behind the last stage.
+template <typename L, typename Next>
+__device__ __forceinline__ void r64_plain_block(f32x16 (&acc3)[2], const float4 (&xc)[8], float2 sc, uint4* lb, const BlockArgs& a, const float (&inv)[3], bool cond,
+                                                const float* cp, int tile, bool store, int lane, int lane_o, int h, float& xmean, float& xm2,
+                                                Next&& next_input) {
+    r64_stages<L, 8>(acc3, xc, sc.x, rsqrtf(sc.y * a.inv_nin + kLnEps), lb, inv[0], inv[1], cond, cp, lane, h);
+    r64_unscale_add<8>(acc3, inv[2], reinterpret_cast<const float*>(lb + L::VEC) + L::C3, h);
+    next_input();
+#pragma unroll
+    for (int G = 0; G < 8; ++G) acc_add_f4<2>(acc3, G, xc[G]);
+    r64_stats_store(acc3, a, tile, store, lane_o, h, xmean, xm2);
+}
 
 // NTO > 0: + the raw Linear that consumes the block (Upsample 64 -> 32 * NTO), its planes resident too; `store_block_out`: the
 // block's own output is a skip tensor somebody else reads
@@ -152,95 +321,30 @@ template <bool SCLIN, int NTO>
 __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, const int ngroups) {
     using L = R64Layout<SCLIN, NTO>;
     const BlockArgsH& ah = A.b;
-    constexpr int N = 64, NT = 2, NG = 8, KS1 = L::KS1, XG = SCLIN ? 16 : 8;       // XG: 8-feature groups of the (concatenated) input
+    constexpr int NT = 2, KS1 = L::KS1, XG = SCLIN ? 16 : 8;       // XG: 8-feature groups of the (concatenated) input
     __shared__ uint4 lds[L::TOTAL_U4];
     float* const vec = reinterpret_cast<float*>(lds + L::VEC);
     const BlockArgs& a = ah.b;
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr float kL2 = -1.44269504088896341f;
-
-    // ---- the block's planes and vectors -> LDS, once per launch.  EVERY load is issued before the first LDS write: written as
-    // `for (i...) lds[i] = src[i]` hipcc emits load -> s_waitcnt vmcnt(0) -> ds_write per iteration, 13 dependent L2 round trips (1 us of
-    // the 5-6 us every launch costs before its first tile: profiles/r03d_fixed_cost.txt)
     {
-        constexpr int N1 = 2 * KS1 * 128 / 512, N2 = 2 * 4 * 128 / 512, NL = (NTO * 4 * 128 + 511) / 512;
-        uint4 r1[N1], r2[N2], r3[N2], rs[SCLIN ? N1 : 1], rl[NTO > 0 ? NL : 1];
-        float g1 = 0.f, b1 = 0.f, bl = 0.f, v6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tb = 0.f;
-        const int tid = threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < N1; ++k) r1[k] = ah.W1h[tid + 512 * k];
-#pragma unroll
-        for (int k = 0; k < N2; ++k) { r2[k] = ah.W2h[tid + 512 * k]; r3[k] = ah.W3h[tid + 512 * k]; }
-        if (SCLIN) {
-#pragma unroll
-            for (int k = 0; k < N1; ++k) rs[k] = ah.Wsch[tid + 512 * k];
-        }
-        if (NTO > 0) {
-#pragma unroll
-            for (int k = 0; k < NL; ++k) {              // (whole 512-piece rounds unconditionally: a conditionally written array element sends
-                rl[k] = make_uint4(0u, 0u, 0u, 0u);     // the array to scratch memory)
-                if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) rl[k] = A.l.Wh[tid + 512 * k];
-            }
-            if (tid < 32 * NTO) bl = A.l.l.bias[tid];
-        }
-        if (tid < 16 * KS1) { g1 = a.gamma1[tid]; b1 = a.beta1[tid]; }
-        if (tid < 64) {
-            v6[0] = a.gamma2[tid]; v6[1] = a.beta2[tid]; v6[2] = a.gamma3[tid]; v6[3] = a.beta3[tid]; v6[4] = a.c2[tid]; v6[5] = a.c3[tid];
-            tb = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + tid];
-        }
-#pragma unroll
-        for (int k = 0; k < N1; ++k) lds[L::W1 + tid + 512 * k] = r1[k];
-#pragma unroll
-        for (int k = 0; k < N2; ++k) { lds[L::W2 + tid + 512 * k] = r2[k]; lds[L::W3 + tid + 512 * k] = r3[k]; }
-        if (SCLIN) {
-#pragma unroll
-            for (int k = 0; k < N1; ++k) lds[L::WSC + tid + 512 * k] = rs[k];
-        }
-        if (NTO > 0) {
-#pragma unroll
-            for (int k = 0; k < NL; ++k)
-                if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) lds[L::WL + tid + 512 * k] = rl[k];
-            if (tid < 32 * NTO) vec[L::BL + tid] = bl;
-        }
-        if (tid < 16 * KS1) { vec[L::G1 + tid] = g1 * kL2; vec[L::B1 + tid] = b1 * kL2; }
-        if (tid < 64) {
-            vec[L::G2 + tid] = v6[0] * kL2; vec[L::B2 + tid] = v6[1] * kL2; vec[L::G3 + tid] = v6[2] * kL2; vec[L::B3 + tid] = v6[3] * kL2;
-            vec[L::C2 + tid] = v6[4]; vec[L::C3 + tid] = v6[5];
-            vec[L::TB + tid] = tb;
-        }
+        R64Staged<SCLIN, NTO> s;
+        r64_staged_load(s, ah, &A.l, threadIdx.x);
+        r64_staged_write(s, lds, threadIdx.x);
     }
-    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
+    const float inv[3] = {ah.kc[0], ah.kc[1], ah.kc[2]};      // the stages' un-scale factors
     float invL = 0.f;
     if (NTO > 0) invL = A.l.kc[0];
     __syncthreads();
     lds_cu4* const wl = (lds_cu4*)(lds + L::WL) + lane;
-    lds_cu4* const w1 = (lds_cu4*)(lds + L::W1) + lane;
-    lds_cu4* const w2 = (lds_cu4*)(lds + L::W2) + lane;
-    lds_cu4* const w3 = (lds_cu4*)(lds + L::W3) + lane;
     lds_cu4* const wsc = (lds_cu4*)(lds + L::WSC) + lane;
-
-    auto tile_of = [&](int g) -> R64Tile {
-        const int traw = g * kR64Waves + wave;
-        const int tile = traw < a.ntiles ? traw : a.ntiles - 1;
-        const int ptile = tile >= a.tiles_per_pass ? tile - a.tiles_per_pass : tile;
-        const int t0 = seg_tile(a.in0, tile), t1 = seg_tile(a.in1, tile);
-        R64Tile t;
-        t.x0 = a.in0.data + (size_t)t0 * 8 * 256 + lane * 4;
-        t.st0 = reinterpret_cast<const float2*>(a.in0.stats) + (size_t)t0 * 32 + j;
-        t.x1 = SCLIN ? a.in1.data + (size_t)t1 * 8 * 256 + lane * 4 : t.x0;
-        t.st1 = SCLIN ? reinterpret_cast<const float2*>(a.in1.stats) + (size_t)t1 * 32 + j : t.st0;
-        t.cp = a.cond_pre + (size_t)ptile * NG * 256 + lane * 4;
-        t.cond = tile >= a.uncond_tiles;
-        return t;
-    };
     auto xsrc = [&](const R64Tile& t, int G) -> const float* { return SCLIN && G >= 8 ? t.x1 + (size_t)(G - 8) * 256 : t.x0 + (size_t)G * 256; };
 
     // the first tile's input
     float4 xc[XG];
     float2 s0c, s1c;
     {
-        const R64Tile t = tile_of(blockIdx.x < ngroups ? blockIdx.x : 0);
+        const R64Tile t = r64_tile<SCLIN>(a, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
 #pragma unroll
         for (int G = 0; G < XG; ++G) xc[G] = ld4(xsrc(t, G));
         s0c = *t.st0; s1c = *t.st1;
@@ -253,112 +357,34 @@ __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, con
         const int tile_raw = g * kR64Waves + wave;
         const bool live = tile_raw < a.ntiles;
         const int tile = live ? tile_raw : a.ntiles - 1;
-        const R64Tile cur = tile_of(g);
-        const R64Tile nxt = tile_of(g + gridDim.x < ngroups ? g + gridDim.x : g);
-        // condition embedding of this tile: requested now, added after stage 2
-        float4 cpv[NG];
-        if (cur.cond) {
-#pragma unroll
-            for (int G = 0; G < NG; ++G) cpv[G] = ld4(cur.cp + (size_t)G * 256);
-        }
-
-        // ---- LN1 statistics (Chan merge over the concat)
-        float mean1, rstd1;
-        {
-            float mean = s0c.x, m2 = s0c.y;
-            if (SCLIN) {
-                const float dd = s1c.x - mean;
-                m2 = m2 + s1c.y + dd * dd * a.chan_w;
-                mean = mean + dd * a.chan_f;
-            }
-            mean1 = mean;
-            rstd1 = rsqrtf(m2 * a.inv_nin + kLnEps);
-            if (SCLIN) range_check(a.range_flag, mean, m2);
-        }
-
-        // ---- stage 1
-        f32x16 acc1[NT];
-        {
-            const float cc = rstd1, dd = -mean1 * rstd1;
-            r64_stage<true, true, KS1>(acc1, w1, KS1 * 128, vec + L::G1, vec + L::B1, cc, dd, h,
-                                       [&](int S, float (&x)[8]) {
-                                           x[0] = xc[2 * S].x; x[1] = xc[2 * S].y; x[2] = xc[2 * S].z; x[3] = xc[2 * S].w;
-                                           x[4] = xc[2 * S + 1].x; x[5] = xc[2 * S + 1].y; x[6] = xc[2 * S + 1].z; x[7] = xc[2 * S + 1].w;
-                                       }, [](int) {});
-        }
-        r64_unscale_add<8>(acc1, inv1, vec + L::TB, h);
-
-        // ---- stage 2
-        f32x16 acc2[NT];
-        {
-            float mean, m2;
-            acc_stats<N, NT>(acc1, h, mean, m2);
-            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-            r64_stage<true, true, 4>(acc2, w2, 4 * 128, vec + L::G2, vec + L::B2, cc, dd, h,
-                                     [&](int S, float (&x)[8]) {
-                                         const int t = S >> 1, r0 = 8 * (S & 1);
-#pragma unroll
-                                         for (int q = 0; q < 8; ++q) x[q] = acc1[t][r0 + q];
-                                     }, [](int) {});
-            r64_unscale_add<8>(acc2, inv2, vec + L::C2, h);
-        }
-        if (cur.cond) {
-#pragma unroll
-            for (int G = 0; G < NG; ++G) {
-                acc2[G >> 2][4 * (G & 3) + 0] += cpv[G].x; acc2[G >> 2][4 * (G & 3) + 1] += cpv[G].y;
-                acc2[G >> 2][4 * (G & 3) + 2] += cpv[G].z; acc2[G >> 2][4 * (G & 3) + 3] += cpv[G].w;
-            }
-        }
-
-        // ---- stage 3
-        f32x16 (&acc3)[NT] = acc1;
-        {
-            float mean, m2;
-            acc_stats<N, NT>(acc2, h, mean, m2);
-            const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps), cc = rstd, dd = -mean * rstd;
-            r64_stage<true, true, 4>(acc3, w3, 4 * 128, vec + L::G3, vec + L::B3, cc, dd, h,
-                                     [&](int S, float (&x)[8]) {
-                                         const int t = S >> 1, r0 = 8 * (S & 1);
-#pragma unroll
-                                         for (int q = 0; q < 8; ++q) x[q] = acc2[t][r0 + q];
-                                     }, [](int) {});
-        }
-
-        // ---- shortcut / residual from the SAME registers stage 1 read; the next tile's input is requested step by step behind it
+        const R64Tile cur = r64_tile<SCLIN>(a, g, wave, lane, j);
+        const R64Tile nxt = r64_tile<SCLIN>(a, g + gridDim.x < ngroups ? g + gridDim.x : g, wave, lane, j);
+        const int lane_o = r64_opaque_lane(lane);
+        const bool store = live && (NTO == 0 || A.store_block_out);
+        f32x16 acc3[NT];
+        float xmean, xm2;
         float4 xn[XG];
         float2 s0n, s1n;
-        s0n = *nxt.st0; s1n = *nxt.st1;
-        if (SCLIN) {
-            r64_stage<false, false, KS1>(acc3, wsc, KS1 * 128, nullptr, nullptr, 0.f, 0.f, h,
-                                         [&](int S, float (&x)[8]) {
-                                             x[0] = xc[2 * S].x; x[1] = xc[2 * S].y; x[2] = xc[2 * S].z; x[3] = xc[2 * S].w;
-                                             x[4] = xc[2 * S + 1].x; x[5] = xc[2 * S + 1].y; x[6] = xc[2 * S + 1].z; x[7] = xc[2 * S + 1].w;
-                                         },
-                                         [&](int S) { xn[2 * S] = ld4(xsrc(nxt, 2 * S)); xn[2 * S + 1] = ld4(xsrc(nxt, 2 * S + 1)); });
-            r64_unscale_add<8>(acc3, inv3, vec + L::C3, h);
+        if constexpr (!SCLIN) {
+            r64_plain_block<L>(acc3, xc, s0c, lds, a, inv, cur.cond, cur.cp, tile, store, lane, lane_o, h, xmean, xm2, [&]() {
+                s0n = *nxt.st0; s1n = s0n;
+#pragma unroll
+                for (int G = 0; G < XG; ++G) xn[G] = ld4(xsrc(nxt, G));
+            });
         } else {
-            r64_unscale_add<8>(acc3, inv3, vec + L::C3, h);
-#pragma unroll
-            for (int G = 0; G < NG; ++G) {
-                acc3[G >> 2][4 * (G & 3) + 0] += xc[G].x; acc3[G >> 2][4 * (G & 3) + 1] += xc[G].y;
-                acc3[G >> 2][4 * (G & 3) + 2] += xc[G].z; acc3[G >> 2][4 * (G & 3) + 3] += xc[G].w;
-                xn[G] = ld4(xsrc(nxt, G));
-            }
-        }
-
-        // ---- statistics + store
-        float xmean, xm2;
-        acc_stats<N, NT>(acc3, h, xmean, xm2);
-        // (the lane index as an opaque value at the two store sites: hipcc otherwise forms the per-lane 64-bit output addresses in the
-        // prologue, keeps them live across the whole tile loop and spills them in the 256-register variants)
-        int lane_o = lane;
-        asm volatile("" : "+v"(lane_o));
-        if (live && (NTO == 0 || A.store_block_out)) {
-            if (lane_o < 32) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + lane_o] = make_float2(xmean, xm2);
-#pragma unroll
-            for (int G = 0; G < NG; ++G)
-                st4(a.out + ((size_t)tile * NG + G) * 256 + lane_o * 4,
-                    make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]));
+            // ---- LN1 statistics: Chan merge over the concat
+            const float dm = s1c.x - s0c.x;
+            const float m2 = s0c.y + s1c.y + dm * dm * a.chan_w;
+            const float mean1 = s0c.x + dm * a.chan_f;
+            const float rstd1 = rsqrtf(m2 * a.inv_nin + kLnEps);
+            range_check(a.range_flag, mean1, m2);
+            r64_stages<L, XG>(acc3, xc, mean1, rstd1, lds, inv[0], inv[1], cur.cond, cur.cp, lane, h);
+            // ---- Linear shortcut from the SAME registers stage 1 read; the next tile's input is requested step by step behind it
+            s0n = *nxt.st0; s1n = *nxt.st1;
+            r64_stage<false, false, KS1>(acc3, wsc, KS1 * 128, nullptr, nullptr, 0.f, 0.f, h, r64_x_regs<XG>(xc),
+                                         [&](int S) { xn[2 * S] = ld4(xsrc(nxt, 2 * S)); xn[2 * S + 1] = ld4(xsrc(nxt, 2 * S + 1)); });
+            r64_unscale_add<8>(acc3, inv[2], vec + L::C3, h);
+            r64_stats_store(acc3, a, tile, store, lane_o, h, xmean, xm2);
         }
         if constexpr (NTO > 0) {
             // ---- the consuming raw Linear: K = 64 (4 k16-steps) from the block's output in registers
@@ -409,9 +435,7 @@ __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, con
                 if (lane_o < 32) reinterpret_cast<float2*>(la.out_stats)[(size_t)tile * 32 + lane_o] = make_float2(m, sq);
 #pragma unroll
                 for (int G = 0; G < NTO * 4; ++G)
-                    if (G < NGo)
-                        st4(la.out + ((size_t)tile * NGo + G) * 256 + lane_o * 4,
-                            make_float4(accL[G >> 2][4 * (G & 3)], accL[G >> 2][4 * (G & 3) + 1], accL[G >> 2][4 * (G & 3) + 2], accL[G >> 2][4 * (G & 3) + 3]));
+                    if (G < NGo) st4(la.out + ((size_t)tile * NGo + G) * 256 + lane_o * 4, acc_f4<NTO>(accL, G));
             }
         }
 #pragma unroll
@@ -422,65 +446,31 @@ __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, con
 
 // ---- two consecutive down-64 blocks (no Linear shortcut, no consuming Linear) in ONE launch: both blocks' planes are resident
 // (2 x 48 KiB), the first block's output is stored (it is a skip tensor) AND handed to the second block in registers -- a launch's
-// fixed cost (5-6 us, profiles/r03d_fixed_cost.txt) and one read of that tensor less per step.  Arithmetic as k_res64_lds<false, 0>.
+// fixed cost (5-6 us, profiles/r03d_fixed_cost.txt) and one read of that tensor less per step.  Both halves are r64_plain_block, the
+// program of k_res64_lds<false, 0>.
 __global__ __launch_bounds__(512, 2) void k_res64_dual(const BlockArgsH A0, const BlockArgsH A1, const int ngroups) {
     using L = R64Layout<false, 0>;
-    constexpr int N = 64, NT = 2, NG = 8, KS1 = 4;
+    constexpr int NT = 2, NG = 8;
     __shared__ uint4 lds[2 * L::TOTAL_U4];
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr float kL2 = -1.44269504088896341f;
-    const int tid = threadIdx.x;
     {   // every load of both blocks first, then the LDS writes
-        uint4 r1[2][2], r2[2][2], r3[2][2];
-        float g1[2] = {0.f, 0.f}, b1[2] = {0.f, 0.f}, v6[2][6], tb[2] = {0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const BlockArgsH& ah = k == 0 ? A0 : A1;
-            const BlockArgs& a = ah.b;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) { r1[k][q] = ah.W1h[tid + 512 * q]; r2[k][q] = ah.W2h[tid + 512 * q]; r3[k][q] = ah.W3h[tid + 512 * q]; }
-            if (tid < 16 * KS1) { g1[k] = a.gamma1[tid]; b1[k] = a.beta1[tid]; }
-#pragma unroll
-            for (int q = 0; q < 6; ++q) v6[k][q] = 0.f;
-            if (tid < 64) {
-                v6[k][0] = a.gamma2[tid]; v6[k][1] = a.beta2[tid]; v6[k][2] = a.gamma3[tid]; v6[k][3] = a.beta3[tid]; v6[k][4] = a.c2[tid]; v6[k][5] = a.c3[tid];
-                tb[k] = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + tid];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            uint4* const lb = lds + k * L::TOTAL_U4;
-            float* const vec = reinterpret_cast<float*>(lb + L::VEC);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) { lb[L::W1 + tid + 512 * q] = r1[k][q]; lb[L::W2 + tid + 512 * q] = r2[k][q]; lb[L::W3 + tid + 512 * q] = r3[k][q]; }
-            if (tid < 16 * KS1) { vec[L::G1 + tid] = g1[k] * kL2; vec[L::B1 + tid] = b1[k] * kL2; }
-            if (tid < 64) {
-                vec[L::G2 + tid] = v6[k][0] * kL2; vec[L::B2 + tid] = v6[k][1] * kL2; vec[L::G3 + tid] = v6[k][2] * kL2; vec[L::B3 + tid] = v6[k][3] * kL2;
-                vec[L::C2 + tid] = v6[k][4]; vec[L::C3 + tid] = v6[k][5];
-                vec[L::TB + tid] = tb[k];
-            }
-        }
+        R64Staged<false, 0> s0, s1;
+        r64_staged_load(s0, A0, nullptr, threadIdx.x);
+        r64_staged_load(s1, A1, nullptr, threadIdx.x);
+        r64_staged_write(s0, lds, threadIdx.x);
+        r64_staged_write(s1, lds + L::TOTAL_U4, threadIdx.x);
     }
+    const float inv[2][3] = {{A0.kc[0], A0.kc[1], A0.kc[2]}, {A1.kc[0], A1.kc[1], A1.kc[2]}};
     __syncthreads();
     const BlockArgs& a0 = A0.b;
-    auto x0_of = [&](int g) -> const float* {
-        const int traw = g * kR64Waves + wave;
-        const int tile = traw < a0.ntiles ? traw : a0.ntiles - 1;
-        return a0.in0.data + (size_t)seg_tile(a0.in0, tile) * 8 * 256 + lane * 4;
-    };
-    auto st0_of = [&](int g) -> const float2* {
-        const int traw = g * kR64Waves + wave;
-        const int tile = traw < a0.ntiles ? traw : a0.ntiles - 1;
-        return reinterpret_cast<const float2*>(a0.in0.stats) + (size_t)seg_tile(a0.in0, tile) * 32 + j;
-    };
     float4 xc[NG];
     float2 sc;
     {
-        const float* xp = x0_of(blockIdx.x < ngroups ? blockIdx.x : 0);
+        const R64Tile t = r64_tile<false>(a0, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
 #pragma unroll
-        for (int G = 0; G < NG; ++G) xc[G] = ld4(xp + (size_t)G * 256);
-        sc = *st0_of(blockIdx.x < ngroups ? blockIdx.x : 0);
+        for (int G = 0; G < NG; ++G) xc[G] = ld4(t.x0 + (size_t)G * 256);
+        sc = *t.st0;
     }
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         asm volatile("" ::: "memory");                   // as k_res64_lds: keeps the plane reads inside the loop
@@ -489,88 +479,26 @@ __global__ __launch_bounds__(512, 2) void k_res64_dual(const BlockArgsH A0, cons
         const int tile = live ? tile_raw : a0.ntiles - 1;
         const int ptile = tile >= a0.tiles_per_pass ? tile - a0.tiles_per_pass : tile;
         const bool cond = tile >= a0.uncond_tiles;
-        const int gn = g + gridDim.x < ngroups ? g + gridDim.x : g;
+        const R64Tile nxt = r64_tile<false>(a0, g + gridDim.x < ngroups ? g + gridDim.x : g, wave, lane, j);
+        const int lane_o = r64_opaque_lane(lane);
         float4 xn[NG];
         float2 sn = sc;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const BlockArgsH& ah = k == 0 ? A0 : A1;
-            const BlockArgs& a = ah.b;
-            lds_cu4* const w1 = (lds_cu4*)(lds + k * L::TOTAL_U4 + L::W1) + lane;
-            lds_cu4* const w2 = (lds_cu4*)(lds + k * L::TOTAL_U4 + L::W2) + lane;
-            lds_cu4* const w3 = (lds_cu4*)(lds + k * L::TOTAL_U4 + L::W3) + lane;
-            const float* const vec = reinterpret_cast<const float*>(lds + k * L::TOTAL_U4 + L::VEC);
-            const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
-            float4 cpv[NG];
-            if (cond) {
-                const float* cp = a.cond_pre + (size_t)ptile * NG * 256 + lane * 4;
-#pragma unroll
-                for (int G = 0; G < NG; ++G) cpv[G] = ld4(cp + (size_t)G * 256);
-            }
-            const float rstd1 = rsqrtf(sc.y * a.inv_nin + kLnEps), mean1 = sc.x;
-            f32x16 acc1[NT];
-            r64_stage<true, true, KS1>(acc1, w1, KS1 * 128, vec + L::G1, vec + L::B1, rstd1, -mean1 * rstd1, h,
-                                       [&](int S, float (&x)[8]) {
-                                           x[0] = xc[2 * S].x; x[1] = xc[2 * S].y; x[2] = xc[2 * S].z; x[3] = xc[2 * S].w;
-                                           x[4] = xc[2 * S + 1].x; x[5] = xc[2 * S + 1].y; x[6] = xc[2 * S + 1].z; x[7] = xc[2 * S + 1].w;
-                                       }, [](int) {});
-            r64_unscale_add<8>(acc1, inv1, vec + L::TB, h);
-            f32x16 acc2[NT];
-            {
-                float mean, m2;
-                acc_stats<N, NT>(acc1, h, mean, m2);
-                const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps);
-                r64_stage<true, true, 4>(acc2, w2, 4 * 128, vec + L::G2, vec + L::B2, rstd, -mean * rstd, h,
-                                         [&](int S, float (&x)[8]) {
-                                             const int t = S >> 1, r0 = 8 * (S & 1);
-#pragma unroll
-                                             for (int q = 0; q < 8; ++q) x[q] = acc1[t][r0 + q];
-                                         }, [](int) {});
-                r64_unscale_add<8>(acc2, inv2, vec + L::C2, h);
-            }
-            if (cond) {
-#pragma unroll
-                for (int G = 0; G < NG; ++G) {
-                    acc2[G >> 2][4 * (G & 3) + 0] += cpv[G].x; acc2[G >> 2][4 * (G & 3) + 1] += cpv[G].y;
-                    acc2[G >> 2][4 * (G & 3) + 2] += cpv[G].z; acc2[G >> 2][4 * (G & 3) + 3] += cpv[G].w;
-                }
-            }
-            f32x16 (&acc3)[NT] = acc1;
-            {
-                float mean, m2;
-                acc_stats<N, NT>(acc2, h, mean, m2);
-                const float rstd = rsqrtf(m2 * (1.0f / N) + kLnEps);
-                r64_stage<true, true, 4>(acc3, w3, 4 * 128, vec + L::G3, vec + L::B3, rstd, -mean * rstd, h,
-                                         [&](int S, float (&x)[8]) {
-                                             const int t = S >> 1, r0 = 8 * (S & 1);
-#pragma unroll
-                                             for (int q = 0; q < 8; ++q) x[q] = acc2[t][r0 + q];
-                                         }, [](int) {});
-            }
-            r64_unscale_add<8>(acc3, inv3, vec + L::C3, h);
-            if (k == 1) {                              // the next tile's input of the FIRST block, behind the residual add
-                const float* xp = x0_of(gn);
-#pragma unroll
-                for (int G = 0; G < NG; ++G) xn[G] = ld4(xp + (size_t)G * 256);
-                sn = *st0_of(gn);
-            }
-#pragma unroll
-            for (int G = 0; G < NG; ++G) {
-                acc3[G >> 2][4 * (G & 3) + 0] += xc[G].x; acc3[G >> 2][4 * (G & 3) + 1] += xc[G].y;
-                acc3[G >> 2][4 * (G & 3) + 2] += xc[G].z; acc3[G >> 2][4 * (G & 3) + 3] += xc[G].w;
-            }
+            const BlockArgs& a = k == 0 ? A0.b : A1.b;
+            f32x16 acc3[NT];
             float xmean, xm2;
-            acc_stats<N, NT>(acc3, h, xmean, xm2);
-            if (live) {
-                if (h == 0) reinterpret_cast<float2*>(a.out_stats)[(size_t)tile * 32 + j] = make_float2(xmean, xm2);
+            r64_plain_block<L>(acc3, xc, sc, lds + k * L::TOTAL_U4, a, inv[k], cond, a.cond_pre + (size_t)ptile * NG * 256 + lane * 4, tile, live, lane,
+                               lane_o, h, xmean, xm2, [&]() {
+                                   if (k == 1) {          // the next tile's input of the FIRST block, behind the second block's last stage
 #pragma unroll
-                for (int G = 0; G < NG; ++G)
-                    st4(a.out + ((size_t)tile * NG + G) * 256 + lane * 4,
-                        make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]));
-            }
+                                       for (int G = 0; G < NG; ++G) xn[G] = ld4(nxt.x0 + (size_t)G * 256);
+                                       sn = *nxt.st0;
+                                   }
+                               });
             if (k == 0) {                              // the second block's input: this block's output, in registers
 #pragma unroll
-                for (int G = 0; G < NG; ++G) xc[G] = make_float4(acc3[G >> 2][4 * (G & 3)], acc3[G >> 2][4 * (G & 3) + 1], acc3[G >> 2][4 * (G & 3) + 2], acc3[G >> 2][4 * (G & 3) + 3]);
+                for (int G = 0; G < NG; ++G) xc[G] = acc_f4<NT>(acc3, G);
                 sc = make_float2(xmean, xm2);
             }
         }

@@ -274,32 +274,6 @@ __device__ __forceinline__ void ln_silu_bwd_acc(f32x16 (&da)[NT], const f32x16 (
         }
 }
 
-template <int NG, int NT>
-__device__ __forceinline__ void acc_load(f32x16 (&a)[NT], const float* __restrict__ p /* tile base + lane*4 */) {
-#pragma unroll
-    for (int G = 0; G < NT * 4; ++G) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (G < NG) v = ld4(p + (size_t)G * 256);
-        a[G >> 2][4 * (G & 3) + 0] = v.x; a[G >> 2][4 * (G & 3) + 1] = v.y;
-        a[G >> 2][4 * (G & 3) + 2] = v.z; a[G >> 2][4 * (G & 3) + 3] = v.w;
-    }
-}
-template <int NG, int NT>
-__device__ __forceinline__ void acc_load_add(f32x16 (&a)[NT], const float* __restrict__ p) {
-#pragma unroll
-    for (int G = 0; G < NG; ++G) {
-        const float4 v = ld4(p + (size_t)G * 256);
-        a[G >> 2][4 * (G & 3) + 0] += v.x; a[G >> 2][4 * (G & 3) + 1] += v.y;
-        a[G >> 2][4 * (G & 3) + 2] += v.z; a[G >> 2][4 * (G & 3) + 3] += v.w;
-    }
-}
-template <int NG, int NT>
-__device__ __forceinline__ void acc_store(const f32x16 (&a)[NT], float* __restrict__ p) {
-#pragma unroll
-    for (int G = 0; G < NG; ++G)
-        st4(p + (size_t)G * 256, make_float4(a[G >> 2][4 * (G & 3)], a[G >> 2][4 * (G & 3) + 1], a[G >> 2][4 * (G & 3) + 2],
-                                             a[G >> 2][4 * (G & 3) + 3]));
-}
 template <int NT>
 __device__ __forceinline__ void acc_zero(f32x16 (&a)[NT]) {
 #pragma unroll
