@@ -93,6 +93,14 @@ __device__ __forceinline__ void glds_stats_s(unsigned voff4, const void* s0, con
                  "s_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff4), "s"(s0), "s"(s1m), "s"(lds_dst) : "memory");
 }
+// one 256-B row (one dword per lane) -> lds_dst
+__device__ __forceinline__ void glds_row_s(unsigned voff4, const void* s0, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dword %1, %2\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff4), "s"(s0), "s"(lds_dst) : "memory");
+}
 
 // The private operand stream of ONE wave: per tile [row statistics | stage 1: KS1 items | condition embedding: 8 items on a
 // conditional tile | shortcut: KS1 items, or the residual re-read: 8 items], an item = 2 KiB (two 8-feature groups of the tile).
@@ -421,22 +429,71 @@ struct PanelWg {
         since_w = 0;
     }
 
-    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e); `more(i)`: further vectors of feature i
-    template <typename More>
-    __device__ __forceinline__ void stage_vectors(const BlockArgs& a, More&& more) {
-        const int n1 = ln1_extent(a);
-        for (int i = threadIdx.x; i < n1; i += NTHR) { g1v[i] = a.gamma1[i] * kL2; b1v[i] = a.beta1[i] * kL2; }
-        if (threadIdx.x < 128) {
-            const int i = threadIdx.x;
-            g2v[i] = a.gamma2[i] * kL2; b2v[i] = a.beta2[i] * kL2; g3v[i] = a.gamma3[i] * kL2; b3v[i] = a.beta3[i] * kL2;
-            c2v[i] = a.c2[i]; c3v[i] = a.c3[i];
-            tbv[i] = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + i];
-            more(i);
+    // ---- per-feature vectors -> LDS, once per launch (LayerNorm vectors times -log2 e).  Called BEHIND prologue(): the launch's first
+    // memory operations are the first tile's operands and panel 0, and everything here rides on the same round trip:
+    //   * every global load goes out before the first LDS write (written as `lds[i] = global[i] * k` statements hipcc emits load -> wait ->
+    //     write per statement, see r64_staged_load); load_more(i, m) / write_more(i, m): up to three further vectors of feature i;
+    //   * the wait of the first write also drains the prologue's requests (hipcc does not count them, and vector-memory operations retire
+    //     in order), which the first tile needs anyway;
+    //   * the time-bias row hangs on *step_ptr, a round trip of its own.  It is first read behind stage 1, so it does not pass through a
+    //     register (whose write hipcc would wait for with vmcnt(0)): two waves send their halves of the row straight into `tbv` by
+    //     LDS-DMA, in front of the barrier.  The request is older than every request of the tile loop, so each of these waves has its
+    //     half in LDS before it passes its first panel_begin() barrier, and stage 1 holds at least one more barrier before the first read.
+    //     An extra operation in flight only makes the counted waits stricter.
+    static constexpr int NG1 = (kLnLdsW1 + NTHR - 1) / NTHR;      // gamma1 / beta1 pieces per thread
+    template <typename LoadMore, typename WriteMore>
+    __device__ __forceinline__ void stage_vectors(const BlockArgs& a, LoadMore&& load_more, WriteMore&& write_more) {
+        // The vectors are staged by the workgroup's LAST waves (feature i = thread index rotated by half the workgroup): the cycle stamps
+        // show the first waves of a workgroup taking the cold instruction and kernel-argument fetches -- their prologue requests are out
+        // 3 000 - 5 000 cycles after the kernel's start, those of the last waves after 1 300 - 2 500 -- so the round trip the staging
+        // barrier waits for starts that much earlier (profiles/launch_preamble_stamps.txt).
+        const int n1 = ln1_extent(a), i = (threadIdx.x + NTHR / 2) % NTHR;
+        const int vwave = (wave + PW / 2) % PW;          // the wave that holds features 64 vwave .. 64 vwave + 63
+        // The step index, as a PER-LANE vector load (the index `zero` is opaque to hipcc): first of the batch below, and its value stays in
+        // a vector register until the time-bias request uses it as part of its per-lane offset, behind the LDS writes, where the batch has
+        // landed.  As a scalar load it either went out in front of the prologue, which then waited for it (scalar loads return out of
+        // order: the kernel-argument loads next to it take lgkmcnt(0)), or behind it as a vector load with vmcnt(0) right there.
+        // Nothing is computed from the value in front of that use either (the empty asm statement there pins it): hipcc schedules inside a
+        // basic block, and whatever it may compute from the value it computes, and waits for, in the load's own block.  Without a step
+        // pointer the load reads a valid word whose value is multiplied by 0.
+        int zero = 0;
+        asm("" : "+v"(zero));
+        int step = (a.step_ptr ? a.step_ptr : reinterpret_cast<const int*>(a.tbias))[zero];
+        const unsigned step_bytes = a.step_ptr ? (unsigned)a.tb_stride * 4u : 0u;
+        float g1[NG1], b1[NG1], v6[6], m[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < NG1; ++k) {
+            g1[k] = 0.f; b1[k] = 0.f;
+            if (i + k * NTHR < n1) { g1[k] = a.gamma1[i + k * NTHR]; b1[k] = a.beta1[i + k * NTHR]; }
         }
-        __syncthreads();                   // no DMA is in flight yet: a plain barrier
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v6[q] = 0.f;
+        if (i < 128) {
+            v6[0] = a.gamma2[i]; v6[1] = a.beta2[i]; v6[2] = a.gamma3[i]; v6[3] = a.beta3[i]; v6[4] = a.c2[i]; v6[5] = a.c3[i];
+            load_more(i, m);
+        }
+        __builtin_amdgcn_sched_barrier(0);          // every load above, every write below
+#pragma unroll
+        for (int k = 0; k < NG1; ++k)
+            if (i + k * NTHR < n1) { g1v[i + k * NTHR] = g1[k] * kL2; b1v[i + k * NTHR] = b1[k] * kL2; }
+        if (i < 128) {
+            g2v[i] = v6[0] * kL2; b2v[i] = v6[1] * kL2; g3v[i] = v6[2] * kL2; b3v[i] = v6[3] * kL2;
+            c2v[i] = v6[4]; c3v[i] = v6[5];
+            write_more(i, m);
+        }
+        stamp(0x03);
+        if (vwave < 2) {
+            const unsigned tb_lds = (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void*)tbv;
+            asm volatile("" : "+v"(step));
+            glds_row_s(c.lane4 + (unsigned)step * step_bytes, a.tbias + vwave * 64, tb_lds + (unsigned)vwave * 256u);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // my LDS writes; the time-bias request stays in flight across the barrier
+        __builtin_amdgcn_s_barrier();
+        stamp(0x04);
     }
 
-    // prologue: the first four private items of this wave's first tile (statistics, three stage-1 items), then panel 0 into buffer 0
+    // prologue: the first four private items of this wave's first tile (statistics, three stage-1 items), then panel 0 into buffer 0.
+    // The kernel's FIRST memory operations: they need nothing but the kernel arguments.
     __device__ __forceinline__ void prologue(const char* st0, const char* st1, const char* x0, const uint4* panel0) {
         priv_issue_stats(c, st0, st1);
         priv_issue(c, x0);
@@ -601,13 +658,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
     const BlockArgs& a = ah.b;
     const int lane = w.lane, h = w.h, j = w.j, wave = w.wave;
     const int stride = gridDim.x;
-    w.stage_vectors(a, [&](int i) {            // + the vectors of the epilogue Linear
-        if (EPI == 2) { w.gLv[i] = A.l.l.gamma[i] * w.kL2; w.bLv[i] = A.l.l.beta[i] * w.kL2; }
-        if (EPI != 0) w.biasLv[i] = i < NTO * 32 ? A.l.l.bias[i] : 0.f;
-    });
-    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
-    float invL = 0.f;
-    if (EPI != 0) invL = A.l.kc[EPI == 2 ? 1 : 0];
+    w.stamp(0x02);
 
     // ---- this wave's 4 KiB of every weight panel: (out tile, two of its STEPS k16-steps)
     const int wnt = wave / (STEPS / 2), wsub = wave % (STEPS / 2);
@@ -633,7 +684,20 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_h(const Bl
     {
         const TilePtrs cur = tile_ptrs<SCLIN, PW>(a, blockIdx.x < ngroups ? blockIdx.x : 0, wave);
         w.prologue(cur.st0, cur.st1, cur.x0, panel_src(0));
+        w.stamp(0x05);
     }
+    w.stage_vectors(a,
+        [&](int i, float (&m)[3]) {            // + the vectors of the epilogue Linear
+            if (EPI == 2) { m[0] = A.l.l.gamma[i]; m[1] = A.l.l.beta[i]; }
+            if (EPI != 0) { if (i < NTO * 32) m[2] = A.l.l.bias[i]; }
+        },
+        [&](int i, const float (&m)[3]) {
+            if (EPI == 2) { w.gLv[i] = m[0] * w.kL2; w.bLv[i] = m[1] * w.kL2; }
+            if (EPI != 0) w.biasLv[i] = m[2];
+        });
+    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
+    float invL = 0.f;
+    if (EPI != 0) invL = A.l.kc[EPI == 2 ? 1 : 0];
     // sources of the concatenated input by k16-step (stage 1 and the shortcut / residual read the same tensors)
     auto xin = [&](const TilePtrs& t, int S) -> const char* { return SCLIN && S >= 8 ? t.x1 + (size_t)(S - 8) * 2048 : t.x0 + (size_t)S * 2048; };
 
@@ -881,8 +945,7 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
     const int lane = w.lane, h = w.h, j = w.j, wave = w.wave;
     const int stride = gridDim.x;
     const int tpp = a.tiles_per_pass;
-    w.stage_vectors(a, [](int) {});
-    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
+    w.stamp(0x02);
 
     // ---- this wave's 4 KiB of every weight panel: (out tile, two of its STEPS k16-steps)
     const int wnt = wave / (STEPS / 2), wsub = wave % (STEPS / 2);
@@ -907,7 +970,10 @@ __global__ __launch_bounds__(64 * panel_pw(STEPS), 2) void k_panel128_duo_h(cons
     {
         const RowPtrs cur = row_ptrs(blockIdx.x < ngroups ? blockIdx.x : 0);
         w.prologue(cur.st0, cur.st0, cur.x0, panel_src(0));
+        w.stamp(0x05);
     }
+    w.stage_vectors(a, [](int, float (&)[3]) {}, [](int, const float (&)[3]) {});
+    const float inv1 = ah.kc[0], inv2 = ah.kc[1], inv3 = ah.kc[2];
 
     for (int g = blockIdx.x; g < ngroups; g += stride) {
         const int row_raw = g * PW + wave;

@@ -16,6 +16,11 @@
 namespace dsg {
 
 constexpr int kR64Waves = 8;
+// which forms request their first tile's input together with the staging loads, in front of the barrier (measurement builds: 0 none,
+// 2 all): 1 = the forms without Linear shortcut
+#ifndef DSG_R64_FIRST_EARLY
+#define DSG_R64_FIRST_EARLY 1
+#endif
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
 
@@ -164,7 +169,8 @@ __device__ __forceinline__ R64Tile r64_tile(const BlockArgs& a, int g, int wave,
 // ---- a block's planes and vectors -> LDS, once per launch, in two phases: r64_staged_load issues EVERY global load into registers,
 // r64_staged_write writes them to the LDS image at `lb`.  A kernel calls all its loads before its first write: written as
 // `for (i...) lds[i] = src[i]` hipcc emits load -> s_waitcnt vmcnt(0) -> ds_write per iteration, 13 dependent L2 round trips (1 us of
-// the 5-6 us every launch costs before its first tile: profiles/r03d_fixed_cost.txt)
+// the 5-6 us every launch cost before its first tile in round 3: profiles/r03d_fixed_cost.txt; what is left of that cost, and of its
+// start-up chain, now: DESIGN.md 3.9, profiles/launch_preamble_fixed_cost.txt)
 template <bool SCLIN, int NTO>
 struct R64Staged {
     static constexpr int KS1 = R64Layout<SCLIN, NTO>::KS1, N1 = 2 * KS1 * 128 / 512, N2 = 2 * 4 * 128 / 512, NL = (NTO * 4 * 128 + 511) / 512;
@@ -175,6 +181,8 @@ template <bool SCLIN, int NTO>
 __device__ __forceinline__ void r64_staged_load(R64Staged<SCLIN, NTO>& s, const BlockArgsH& ah, const LinArgsH* lin /* NTO > 0 */, int tid) {
     using S = R64Staged<SCLIN, NTO>;
     const BlockArgs& a = ah.b;
+    // the time-bias row hangs on *step_ptr: that load goes out first and has the whole batch of plane loads to come back under
+    const int step = a.step_ptr ? *a.step_ptr : 0;
     s.g1 = 0.f; s.b1 = 0.f; s.bl = 0.f; s.tb = 0.f;
 #pragma unroll
     for (int q = 0; q < 6; ++q) s.v6[q] = 0.f;
@@ -192,13 +200,17 @@ __device__ __forceinline__ void r64_staged_load(R64Staged<SCLIN, NTO>& s, const 
             s.rl[k] = make_uint4(0u, 0u, 0u, 0u);   // the array to scratch memory)
             if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) s.rl[k] = lin->Wh[tid + 512 * k];
         }
-        if (tid < 32 * NTO) s.bl = lin->l.bias[tid];
+        s.bl = lin->l.bias[tid % (32 * NTO)];
     }
-    if (tid < 16 * S::KS1) { s.g1 = a.gamma1[tid]; s.b1 = a.beta1[tid]; }
-    if (tid < 64) {
-        s.v6[0] = a.gamma2[tid]; s.v6[1] = a.beta2[tid]; s.v6[2] = a.gamma3[tid]; s.v6[3] = a.beta3[tid]; s.v6[4] = a.c2[tid]; s.v6[5] = a.c3[tid];
-        s.tb = a.tbias[(size_t)(a.step_ptr ? *a.step_ptr : 0) * a.tb_stride + tid];
-    }
+    // The per-feature vectors: EVERY wave loads them and (r64_staged_write) writes them, the same values to the same places, so that
+    // neither side sits in a branch.  Under `if (tid < 64)` hipcc gave these loads a branch of their own, moved the scaling of
+    // r64_staged_write into it and waited there for each of them; with only the writes in a branch it sank the loads into that one:
+    // either way a round trip of their own in front of or behind the batch of plane loads.
+    const int t1 = tid % (16 * S::KS1), t2 = tid % 64;
+    s.g1 = a.gamma1[t1]; s.b1 = a.beta1[t1];
+    s.v6[0] = a.gamma2[t2]; s.v6[1] = a.beta2[t2]; s.v6[2] = a.gamma3[t2]; s.v6[3] = a.beta3[t2]; s.v6[4] = a.c2[t2]; s.v6[5] = a.c3[t2];
+    // last of the batch (and written last by r64_staged_write)
+    s.tb = a.tbias[(size_t)step * a.tb_stride + t2];
 }
 template <bool SCLIN, int NTO>
 __device__ __forceinline__ void r64_staged_write(const R64Staged<SCLIN, NTO>& s, uint4* lb, int tid) {
@@ -218,14 +230,14 @@ __device__ __forceinline__ void r64_staged_write(const R64Staged<SCLIN, NTO>& s,
 #pragma unroll
         for (int k = 0; k < S::NL; ++k)
             if (512 * (k + 1) <= NTO * 4 * 128 || tid + 512 * k < NTO * 4 * 128) lb[L::WL + tid + 512 * k] = s.rl[k];
-        if (tid < 32 * NTO) vec[L::BL + tid] = s.bl;
+        vec[L::BL + tid % (32 * NTO)] = s.bl;
     }
-    if (tid < 16 * S::KS1) { vec[L::G1 + tid] = s.g1 * kL2; vec[L::B1 + tid] = s.b1 * kL2; }
-    if (tid < 64) {
-        vec[L::G2 + tid] = s.v6[0] * kL2; vec[L::B2 + tid] = s.v6[1] * kL2; vec[L::G3 + tid] = s.v6[2] * kL2; vec[L::B3 + tid] = s.v6[3] * kL2;
-        vec[L::C2 + tid] = s.v6[4]; vec[L::C3 + tid] = s.v6[5];
-        vec[L::TB + tid] = s.tb;
-    }
+    // (every wave writes the vectors: see r64_staged_load)
+    const int t1 = tid % (16 * S::KS1), t2 = tid % 64;
+    vec[L::G1 + t1] = s.g1 * kL2; vec[L::B1 + t1] = s.b1 * kL2;
+    vec[L::G2 + t2] = s.v6[0] * kL2; vec[L::B2 + t2] = s.v6[1] * kL2; vec[L::G3 + t2] = s.v6[2] * kL2; vec[L::B3 + t2] = s.v6[3] * kL2;
+    vec[L::C2 + t2] = s.v6[4]; vec[L::C3 + t2] = s.v6[5];
+    vec[L::TB + t2] = s.tb;
 }
 
 // ---- the block program of one row tile, in pieces.  The eight input values of k16-step S: from a tile in fragment registers (two
@@ -327,28 +339,33 @@ __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, con
     const BlockArgs& a = ah.b;
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    auto xsrc = [&](const R64Tile& t, int G) -> const float* { return SCLIN && G >= 8 ? t.x1 + (size_t)(G - 8) * 256 : t.x0 + (size_t)G * 256; };
+    // One batch of loads in front of the launch's only barrier: the block's image AND the first tile's input (the accumulators are not
+    // live yet, so both fit the registers); the LDS writes follow the last load.  Behind the barrier the first tile starts from
+    // registers instead of from a cold round trip.  Only the forms without Linear shortcut: with one, the same order
+    // measured 1 - 2 us per launch SLOWER (16 KiB of input per wave beside 96 KiB of planes: profiles/launch_preamble_parts.txt).
+    constexpr bool FIRST_EARLY = DSG_R64_FIRST_EARLY == 2 || (DSG_R64_FIRST_EARLY == 1 && !SCLIN);
+    float4 xc[XG];
+    float2 s0c, s1c;
+    auto first_input = [&]() {
+        const R64Tile t = r64_tile<SCLIN>(a, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
+#pragma unroll
+        for (int G = 0; G < XG; ++G) xc[G] = ld4(xsrc(t, G));
+        s0c = *t.st0; s1c = *t.st1;
+    };
     {
         R64Staged<SCLIN, NTO> s;
         r64_staged_load(s, ah, &A.l, threadIdx.x);
+        if constexpr (FIRST_EARLY) first_input();
         r64_staged_write(s, lds, threadIdx.x);
     }
     const float inv[3] = {ah.kc[0], ah.kc[1], ah.kc[2]};      // the stages' un-scale factors
     float invL = 0.f;
     if (NTO > 0) invL = A.l.kc[0];
     __syncthreads();
+    if constexpr (!FIRST_EARLY) first_input();
     lds_cu4* const wl = (lds_cu4*)(lds + L::WL) + lane;
     lds_cu4* const wsc = (lds_cu4*)(lds + L::WSC) + lane;
-    auto xsrc = [&](const R64Tile& t, int G) -> const float* { return SCLIN && G >= 8 ? t.x1 + (size_t)(G - 8) * 256 : t.x0 + (size_t)G * 256; };
-
-    // the first tile's input
-    float4 xc[XG];
-    float2 s0c, s1c;
-    {
-        const R64Tile t = r64_tile<SCLIN>(a, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
-#pragma unroll
-        for (int G = 0; G < XG; ++G) xc[G] = ld4(xsrc(t, G));
-        s0c = *t.st0; s1c = *t.st1;
-    }
 
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         // the planes in LDS never change inside this loop: without a compiler barrier hipcc hoists ALL the plane reads out of it (loop-
@@ -446,7 +463,8 @@ __global__ __launch_bounds__(512, 2) void k_res64_lds(const BlockLinArgsH A, con
 
 // ---- two consecutive down-64 blocks (no Linear shortcut, no consuming Linear) in ONE launch: both blocks' planes are resident
 // (2 x 48 KiB), the first block's output is stored (it is a skip tensor) AND handed to the second block in registers -- a launch's
-// fixed cost (5-6 us, profiles/r03d_fixed_cost.txt) and one read of that tensor less per step.  Both halves are r64_plain_block, the
+// fixed cost (5-6 us when this was built, profiles/r03d_fixed_cost.txt; 3-5 us by the intercepts of profiles/launch_preamble_fixed_cost.txt)
+// and one read of that tensor less per step.  Both halves are r64_plain_block, the
 // program of k_res64_lds<false, 0>.
 __global__ __launch_bounds__(512, 2) void k_res64_dual(const BlockArgsH A0, const BlockArgsH A1, const int ngroups) {
     using L = R64Layout<false, 0>;
@@ -454,24 +472,26 @@ __global__ __launch_bounds__(512, 2) void k_res64_dual(const BlockArgsH A0, cons
     __shared__ uint4 lds[2 * L::TOTAL_U4];
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    {   // every load of both blocks first, then the LDS writes
+    const BlockArgs& a0 = A0.b;
+    float4 xc[NG];
+    float2 sc;
+    auto first_input = [&]() {
+        const R64Tile t = r64_tile<false>(a0, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
+#pragma unroll
+        for (int G = 0; G < NG; ++G) xc[G] = ld4(t.x0 + (size_t)G * 256);
+        sc = *t.st0;
+    };
+    {   // every load of both blocks and of the first tile's input first, then the LDS writes (as k_res64_lds)
         R64Staged<false, 0> s0, s1;
         r64_staged_load(s0, A0, nullptr, threadIdx.x);
         r64_staged_load(s1, A1, nullptr, threadIdx.x);
+        if constexpr (DSG_R64_FIRST_EARLY != 0) first_input();
         r64_staged_write(s0, lds, threadIdx.x);
         r64_staged_write(s1, lds + L::TOTAL_U4, threadIdx.x);
     }
     const float inv[2][3] = {{A0.kc[0], A0.kc[1], A0.kc[2]}, {A1.kc[0], A1.kc[1], A1.kc[2]}};
     __syncthreads();
-    const BlockArgs& a0 = A0.b;
-    float4 xc[NG];
-    float2 sc;
-    {
-        const R64Tile t = r64_tile<false>(a0, blockIdx.x < ngroups ? blockIdx.x : 0, wave, lane, j);
-#pragma unroll
-        for (int G = 0; G < NG; ++G) xc[G] = ld4(t.x0 + (size_t)G * 256);
-        sc = *t.st0;
-    }
+    if constexpr (DSG_R64_FIRST_EARLY == 0) first_input();
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         asm volatile("" ::: "memory");                   // as k_res64_lds: keeps the plane reads inside the loop
         const int tile_raw = g * kR64Waves + wave;

@@ -4,7 +4,8 @@ run with the same variable set; full panels: the stamp area only fits beside the
     python tools/duo_stamps.py [B]
 cfg_share 0: k_panel128_h<false, 0, 1, 4>, a wave walks two tiles; 1: k_panel128_duo_h<4>, a wave walks one row tile.
 Tags as tools/panel_stamps.py (01 group start; S0 row statistics done; S1 step 0 prepared; S4 panel begun; S2 panel's MFMA stream done;
-13 / 23 stage epilogue; 33 condition embedding added; 43 stage 3 un-scaled and residual added; 50 stored).  The last stamped launch of
+13 / 23 stage epilogue; 33 condition embedding added; 43 stage 3 un-scaled and residual added; 50 stored; the launch preamble: 02 init
+done, 05 prologue's requests issued, 03 per-feature vectors loaded and written to LDS, 04 staging barrier passed).  The last stamped launch of
 the call is read: the final step's down.0.  The stamps write LDS: the stamped binary's RESULTS are not valid, only its timing."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,3 +45,6 @@ for val in (0, 1):
         for (t, tag), (p, _) in zip(st[1:], st[:-1]):
             tot[GROUP.get(tag, hex(tag))] = tot.get(GROUP.get(tag, hex(tag)), 0) + t - p
         print(f"  wave {w}: first stamp {st[0][0] - t0 if n >= 8 * 128 + 4 else 0} cycles after the kernel's start, {st[-1][0] - st[0][0]} cycles first to last stamp; by kind: {tot}")
+        if n >= 8 * 128 + 4:      # the launch preamble: every stamp up to the first stage-1 panel, cycles after the kernel's start
+            k1 = next((k for k, (_, tag) in enumerate(st) if tag == 0x14), len(st) - 1)
+            print(f"  wave {w}: preamble " + " ".join(f"{tag:02x}@{t - t0}" for t, tag in st[:k1 + 1]))

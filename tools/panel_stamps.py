@@ -3,7 +3,8 @@
     python tools/panel_stamps.py [op] [B]
 Tags (stage S: 1 stage 1, 2 stage 2, 3 stage 3, 4 shortcut): 01 group start; S0 = the stage's row statistics done; S1 = step 0's operand
 prepared (outside the MFMA stream); S4 = panel begun (weights waited, barrier, next panel issued); S2 = panel's MFMA stream done (with the
-next step's operand prepared inside it); 13 / 23 / 43 = stage epilogue (un-scale, condition term); 50 = stored.  The stamps write LDS:
+next step's operand prepared inside it); 13 / 23 / 43 = stage epilogue (un-scale, condition term); 50 = stored; the launch preamble: 02 =
+init done, 05 = prologue's requests issued, 03 = per-feature vectors loaded and written to LDS, 04 = staging barrier passed.  The stamps write LDS:
 the stamped binary's RESULTS are not valid, only its timing."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,6 +40,9 @@ for w in range(8):
         continue
     t0 = st[0][0]
     print(f"wave {w}: " + " ".join(f"{tag:02x}:{t - p}" for (t, tag), (p, _) in zip(st[1:], st[:-1])) + f"  | total {st[-1][0] - t0}")
+    if n >= 8 * 128 + 4:      # the launch preamble: every stamp up to the first stage-1 panel, cycles after the kernel's start
+        k1 = next((k for k, (_, tag) in enumerate(st) if tag == 0x14), len(st) - 1)
+        print(f"wave {w}: preamble " + " ".join(f"{tag:02x}@{t - buf[8 * 128]}" for t, tag in st[:k1 + 1]))
 
 # merged absolute timeline of the two waves that share SIMD 0 (waves 0 and 4), second tile group
 ev = []
