@@ -151,6 +151,7 @@ class _Native:
         self.step_grid = None             # (handle, plan, its coef on the device), or None: dsg_set_step_grid
         self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
         self.step_guidance = None         # (handle, the weights as a tuple of floats, their tensor, its version), or None: dsg_set_step_guidance
+        self.env_out_key = None           # the `bound_key` whose weights a range query found outside the split envelope, or None
         _NATIVES.add(self)
 
     def __deepcopy__(self, memo):
@@ -323,8 +324,16 @@ class UNet1D(nn.Module):
     def range_exceeded(self):
         """True if, since the last query, a raw operand of the split-f16 path left fp16's range (dsg_range_status_stream:
         synchronises torch's CURRENT stream of the model's device -- the stream the launches went to -- and clears the flag; other
-        streams keep running).  Outputs computed meanwhile are then wrong."""
-        hit = False
+        streams keep running), or if the bound weights are outside the split path's envelope (`range_status`).  Outputs computed
+        meanwhile are then wrong."""
+        return self.range_status() != 0
+
+    def range_status(self):
+        """The bits of `dsg_range_status_stream` over every handle of the module: 1 -- since the last query a raw operand or the condition
+        left fp16's range (cleared by the query); 2 -- the bound WEIGHTS are outside the split path's envelope (a LayerNorm with
+        16 * (max|gamma| * sqrt(features) + max|beta|) > 6e4, or a Linear with max|W| >= 2^21): not cleared, the next
+        bind recomputes it.  Either way the split-f16 results are not to be trusted."""
+        bits = 0
         # every handle that EXISTS (a module that has not launched anything has no flag to read; the twin handle of a split training
         # step has a flag word of its own)
         for nat in [self._native] + list(self.__dict__.get("_twins", {}).values()):
@@ -334,12 +343,26 @@ class UNet1D(nn.Module):
             flag = ctypes.c_int(0)
             with torch.cuda.device(self._named_param_list()[0][1].device):
                 _lib.check(_lib.lib().dsg_range_status_stream(hd, ctypes.byref(flag), _lib.stream_ptr()))
-            hit = hit or bool(flag.value)
-        return hit
+            bits |= flag.value
+            if self.precision == "split_f16":        # (the exact mode reports nothing about the weights: what is known stays)
+                nat.env_out_key = nat.bound_key if flag.value & 2 else None
+        return bits
+
+    def weights_known_outside_envelope(self):
+        """True if a range query since the last bind of the CURRENT weights reported them outside the split envelope (bit 2 of
+        `range_status`).  Costs no device work: it binds changed weights, as every call does, and compares what the query remembered."""
+        self.native_handle()
+        nat = self._native
+        return nat.env_out_key is not None and nat.env_out_key == nat.bound_key
 
     def check_range(self):
-        """Raise if `range_exceeded()`: the caller should switch to `set_precision("f32")` and repeat the call."""
-        if self.range_exceeded():
+        """Raise if `range_exceeded()`, naming the reason: the caller should switch to `set_precision("f32")` and repeat the call."""
+        bits = self.range_status()
+        if bits & 2:
+            raise RuntimeError("libdiffsg_hip: the weights are outside the envelope of the split-f16 path (a LayerNorm with "
+                               "16 * (max|gamma| * sqrt(features) + max|beta|) > 6e4, or a Linear with max|W| >= 2^21); "
+                               "its results are invalid for these weights -- use set_precision('f32') for this model")
+        if bits:
             raise RuntimeError("libdiffsg_hip: an activation exceeded the fp16 range of the split-f16 path (|x| > 6e4); "
                                "the results of the last calls are invalid -- use set_precision('f32') for this model")
 

@@ -104,17 +104,19 @@ int dsg_bind_weights(dsg_handle* h, const float* const* ptrs, int n, void* strea
         HIPCK(hipMemcpyAsync(h->tdesc_dev, td.data(), td.size() * sizeof(TimeBlockDesc), hipMemcpyHostToDevice, s));
         HIPCK(hipStreamSynchronize(s));  // pd / td are host temporaries
     }
-    // (k_pack_grouped also clears the max|W| words for k_maxabs; its grid of >= params / 256 blocks covers them)
-    if ((long long)h->pack_blocks * 256 < (long long)h->params.size()) return fail("internal: pack grid smaller than the parameter table");
-    hipLaunchKernelGGL(k_pack_grouped, dim3((unsigned)h->pack_blocks), dim3(256), 0, s, h->pack_dev, h->pack_n, h->maxabs, (int)h->params.size());
+    // (k_pack_grouped also clears the max|W| words for k_maxabs, and behind them the word "weights outside the split envelope" of the
+    // previous bind; its grid of >= (params + 1) / 256 blocks covers them)
+    if ((long long)h->pack_blocks * 256 < (long long)h->params.size() + 1) return fail("internal: pack grid smaller than the parameter table");
+    hipLaunchKernelGGL(k_pack_grouped, dim3((unsigned)h->pack_blocks), dim3(256), 0, s, h->pack_dev, h->pack_n, h->maxabs, (int)h->params.size() + 1);
     if (h->mx_n) {
         // max|W| of every split-packed weight -> maxabs[param index]; the pack and the block kernels derive the same
         // power-of-two scale from it on the device (no host round trip); k_pack_h also writes the operators' un-scale constants
         hipLaunchKernelGGL(k_maxabs, dim3(h->mx_n, kMaxabsSlices), dim3(256), 0, s, h->mx_ptrs_dev, h->mx_numel_dev, h->mx_idx_dev, h->maxabs);
         const int nopc = (int)(h->res.size() + h->lin.size());
-        if ((long long)h->packh_blocks * 256 < nopc) return fail("internal: plane-pack grid smaller than the operator table");
+        if ((long long)h->packh_blocks * 256 < nopc || (long long)h->packh_blocks * 256 < h->env_n)
+            return fail("internal: plane-pack grid smaller than the operator table");
         hipLaunchKernelGGL(k_pack_h, dim3((unsigned)h->packh_blocks), dim3(256), 0, s, h->packh_dev, h->packh_n, (const float*)h->maxabs,
-                           (const OpConstDesc*)h->opc_desc_dev, nopc, h->opc_dev);
+                           (const OpConstDesc*)h->opc_desc_dev, nopc, h->opc_dev, (const EnvDesc*)h->env_dev, h->env_n, h->env_word());
     }
     // the LDS image of the narrow run (k_fused_narrow_lds) is a COPY of arena pieces: re-gather it from the planes packed above,
     // into the same buffer (cached graphs keep its pointer) -- otherwise sample() after an optimizer step, load_state_dict or an
@@ -272,8 +274,13 @@ int dsg_range_status(dsg_handle* h, int* exceeded) {
     if (!h || !exceeded) return fail("dsg_range_status: null argument");
     DeviceGuard dg(h);
     HIPCK(hipDeviceSynchronize());
+    float env = 0.f;
     HIPCK(hipMemcpy(exceeded, h->range_flag, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&env, h->env_word(), sizeof(float), hipMemcpyDeviceToHost));
     if (*exceeded) HIPCK(hipMemset(h->range_flag, 0, sizeof(int)));
+    // (the weights matter to the split path alone: under DSG_PRECISION_F32_MFMA the handle has nothing to report about them)
+    // (and before the first bind the word has not been written)
+    *exceeded = (*exceeded ? DSG_RANGE_ACTIVATION : 0) | (env != 0.f && h->use_split && h->bound ? DSG_RANGE_WEIGHTS : 0);
     return 0;
 }
 
@@ -285,10 +292,10 @@ int dsg_range_status_stream(dsg_handle* h, int* exceeded, void* stream) {
     // "copy, then memset" lost a flag raised between the two by kernels of another stream -- twin handles, the side stream).  The pinned word
     // belongs to the handle; the copy is truly asynchronous and only `s` is waited for.
     if (!h->range_pinned) HIPCK(h->range_pinned.alloc(1));
-    hipLaunchKernelGGL(k_flag_take, dim3(1), dim3(64), 0, s, h->range_flag, h->range_pinned);
+    hipLaunchKernelGGL(k_flag_take, dim3(1), dim3(64), 0, s, h->range_flag, (const float*)h->env_word(), h->range_pinned);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(s));
-    *exceeded = *h->range_pinned;
+    *exceeded = *h->range_pinned & (h->use_split && h->bound ? ~0 : ~DSG_RANGE_WEIGHTS);     // as in dsg_range_status
     return 0;
 }
 
@@ -322,7 +329,7 @@ int dsg_unet_forward(dsg_handle* h, const float* x, const float* t, const float*
     run_time_path(h, B, s);
     const int tpp = cdiv(B, 32), CG = groups_of(h->d.cond_dim);
     hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tpp * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, h->d.cond_dim, CG,
-                       h->fw.condfrag, tpp);
+                       h->fw.condfrag, tpp, h->use_split ? h->range_flag : nullptr, kCondLimit);
     // the handle's precision mode applies here as in dsg_sample / dsg_train_step: the split kernels take the condition embedding
     // Wc silu(cond * mask) precomputed (a masked row contributes exactly 0), the exact-f32 kernels compute it in the block
     if (h->use_split) run_cond_embed(h, B, s);

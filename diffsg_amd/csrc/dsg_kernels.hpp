@@ -38,11 +38,14 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 // product and the low part of log2 e folded back in (2^(t+e) ~ 2^t (1 + e ln 2)), so the result stays within ~2 ulp of
 // expf() at a third of its VALU cost; a bare v_exp_f32(-v*log2e) is |v|*6e-8 off, which at omega = 500 tripled the
 // end-to-end deviation from the float64 trajectory.
+// The exponent is held at 127: beyond v = -88.7 the power is inf, and inf times the correction term (0 or negative) made the result --
+// and silu(v), which is -0 there -- NaN.  LayerNorm outputs of ordinary weights (|u| <= sqrt(width)) never come near; a large gamma
+// or a condition entry below -88 does, and this is the path such a model is sent to.
 __device__ __forceinline__ float fast_exp_neg(float v) {
     constexpr float c_hi = -1.44269504088896341f, c_lo = -1.925963033500671e-08f;  // -log2(e) split
     const float t = v * c_hi;
     const float e = fmaf(v, c_lo, fmaf(v, c_hi, -t));
-    const float p = __builtin_amdgcn_exp2f(t);
+    const float p = __builtin_amdgcn_exp2f(fminf(t, 127.0f));
     return fmaf(p * e, 0.693147180559945f, p);
 }
 __device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + fast_exp_neg(v)); }
@@ -1143,8 +1146,11 @@ __global__ __launch_bounds__(256) void k_time_table(const float* __restrict__ st
 }
 
 // condfrag[tile][g][lane][p] = silu(cond[row][8g+4h+p] * mask[row])   (UNetCF.py:330 and :93)
+// `range_flag` (split path; null on the exact path): raised where |silu| > `limit` -- the split kernels multiply these fragments by the
+// activation scale and split them into fp16 halves without a LayerNorm in front (k_cond_embed_h, the training weight gradients), and
+// silu is unbounded.  Nothing that is stored changes.
 __global__ void k_cond_frag(const float* __restrict__ cond, const float* __restrict__ mask, int nrows, int C, int CG,
-                            float* __restrict__ out, int ntiles) {
+                            float* __restrict__ out, int ntiles, int* __restrict__ range_flag, float limit) {
     const size_t total = (size_t)ntiles * CG * 256;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int p = idx & 3, lane = (idx >> 2) & 63;
@@ -1157,6 +1163,7 @@ __global__ void k_cond_frag(const float* __restrict__ cond, const float* __restr
             v = cond[(size_t)row * C + f];
             if (mask) v *= mask[row];
             v = silu(v);
+            if (range_flag && fabsf(v) > limit) *range_flag = 1;
         }
         out[idx] = v;
     }
@@ -1489,10 +1496,11 @@ __global__ void k_ema(float* __restrict__ avg, const float* __restrict__ p, floa
 // double from pow(beta, step) and handed on as floats; step size, square root, quotient and the parameter update are float operations.
 // torch's kernel gives a block 65 536 elements of a tensor: the 1.6 M-element flat parameter vector runs on 26 of 256 CUs (45 us); this
 // one is a plain grid-stride loop over 16-byte pieces (memory-bound: 4 reads + 3 writes per element).
-// dsg_range_status_stream: take the flag (read and clear in ONE atomic step) and hand it to the host through a pinned word
-__global__ void k_flag_take(int* __restrict__ flag, int* __restrict__ host_word) {
+// dsg_range_status_stream: take the flag (read and clear in ONE atomic step) and hand it to the host through a pinned word, together with
+// the bind-time word "weights outside the split envelope" (DSG_RANGE_WEIGHTS beside DSG_RANGE_ACTIVATION; read, not cleared: the next bind recomputes it)
+__global__ void k_flag_take(int* __restrict__ flag, const float* __restrict__ env_word, int* __restrict__ host_word) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const int v = atomicExch(flag, 0);
+        const int v = (atomicExch(flag, 0) ? 1 : 0) | (*env_word != 0.f ? 2 : 0);
         __atomic_store_n(host_word, v, __ATOMIC_RELAXED);
         __threadfence_system();
     }

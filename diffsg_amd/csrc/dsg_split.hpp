@@ -34,6 +34,17 @@ constexpr float kRawLimit = 6.0e4f / kRawScale;
 __device__ __forceinline__ void range_check(int* flag, float mean, float m2) {
     if (flag && fabsf(mean) + sqrtf(m2) > kRawLimit) *flag = 1;
 }
+// The other operands of the split products, and what bounds them ("the envelope"):
+//   * the condition: kActScale * silu(cond * mask) is split with no LayerNorm in front -- k_cond_frag raises the same flag above
+//     kCondLimit (a condition entry of about 3 750);
+//   * LayerNorm + SiLU operands: |kActScale * silu(gamma * xhat + beta)| <= kActScale * (max|gamma| * sqrt(N) + max|beta|), since
+//     |xhat| <= sqrt(N) and |silu(u)| <= |u|: a property of the WEIGHTS, checked at bind time against the same 6e4;
+//   * the weights themselves: scale_exp clamps the exponent to [-8, 24], so the planes sit in [4096, 8192) only for max|W| < 2^21.
+// The two weight-side conditions set the handle's word "weights outside the split envelope" (k_pack_h), which dsg_range_status reports
+// as DSG_RANGE_WEIGHTS beside the flag (DSG_RANGE_ACTIVATION).
+constexpr float kCondLimit = 6.0e4f / kActScale;
+constexpr float kWeightLimit = 2097152.0f;     // 2^21
+struct EnvDesc { int w, b; float sqrt_n; };    // LayerNorm: parameter indices of gamma and beta, sqrt(features); Linear: w, b = -1
 
 // Weight scale exponent of one Linear from max|W|: max|W| * 2^e in [4096, 8192).
 __device__ __forceinline__ int scale_exp(float maxabs) {
@@ -2034,10 +2045,19 @@ struct PackHDesc {
 
 // Blocks [0, ceil(nopc / 256)) also write the un-scale constants of the operators (they need the same final
 // max|W| words as the packing, so they ride in this launch instead of one of their own).
+// Blocks [0, ceil(nenv / 256)) check the weight-side envelope (EnvDesc; `maxabs` holds max|gamma| and max|beta| of the LayerNorms too)
+// and raise `env_word`, which k_pack_grouped cleared at the start of this bind.
 __global__ __launch_bounds__(256) void k_pack_h(const PackHDesc* __restrict__ descs, int ndesc, const float* __restrict__ maxabs,
-                                                const OpConstDesc* __restrict__ opc_desc, int nopc, float* __restrict__ opc_out) {
+                                                const OpConstDesc* __restrict__ opc_desc, int nopc, float* __restrict__ opc_out,
+                                                const EnvDesc* __restrict__ env, int nenv, float* __restrict__ env_word) {
     {
         const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i < nenv) {
+            const EnvDesc d = env[i];
+            const bool out = d.b < 0 ? maxabs[d.w] >= kWeightLimit
+                                     : kActScale * (maxabs[d.w] * d.sqrt_n + maxabs[d.b]) > kRawLimit * kRawScale;
+            if (out) *env_word = 1.f;
+        }
         if (i < nopc) {
             const OpConstDesc c = opc_desc[i];
             if (c.w2 < 0) {          // Linear

@@ -152,8 +152,25 @@ int build_plane_tables(dsg_handle* h) {
         PackHDesc& dv = hd.back();
         dv.W = P[t.proj.w].ptr + 2 * (size_t)t.N * t.N; dv.m_self = h->maxabs + t.proj.w;
     }
+    // the weight-side envelope (dsg_split.hpp, EnvDesc): every Linear listed above, and every LayerNorm that feeds a split product --
+    // their max|gamma| and max|beta| are two more words of the same k_maxabs launch.  Conservative in one place: the 8-wide blocks are
+    // listed too, although with DSG_OPT_NARROW_VALU8 on they run in exact float32 on the vector unit -- a large gamma there alone sends
+    // the model to the exact path without need (the option can be switched off at any time, the word is per bind).  Not covered: k_maxabs
+    // reduces with fmaxf, which drops a NaN, so a NaN gamma or weight does not raise the word (the outputs are NaN on either path).
+    std::vector<EnvDesc> env;
+    for (int w : h->mx_param) env.push_back(EnvDesc{w, -1, 0.f});
+    auto want_norm = [&](const NormP& n) {
+        if (n.w < 0 || n.b < 0) return;
+        for (int p : {n.w, n.b}) { h->mx_param.push_back(p); mp.push_back(P[p].ptr); mn.push_back(P[p].numel); }
+        env.push_back(EnvDesc{n.w, n.b, sqrtf((float)P[n.w].numel)});
+    };
+    for (const ResP& r : h->res) { want_norm(r.n1); want_norm(r.n2); want_norm(r.n3); }
+    for (const LinOpP& l : h->lin) if (l.lnact) want_norm(l.ln);
+    h->env_n = (int)env.size();
     h->mx_n = (int)mp.size(); h->packh_n = (int)hd.size(); h->packh_blocks = hb;
     if (h->mx_n) {
+        if (!h->env_dev) HIPCK(h->env_dev.alloc(env.size()));
+        HIPCK(hipMemcpy(h->env_dev, env.data(), env.size() * sizeof(EnvDesc), hipMemcpyHostToDevice));
         if (!h->mx_ptrs_dev) {
             HIPCK(h->mx_ptrs_dev.alloc(mp.size()));
             HIPCK(h->mx_numel_dev.alloc(mn.size()));

@@ -182,6 +182,10 @@ struct dsg_handle {
     std::vector<int> mx_param;         // param index of each k_maxabs block
     DevBuf<PackHDesc> packh_dev; int packh_n = 0; long long packh_blocks = 0;
     DevBuf<OpConstDesc> opc_desc_dev; DevBuf<float> opc_dev;   // [res | lin][4]: un-scale factors, refreshed at every bind (k_pack_h)
+    // the weight-side envelope of the split path (dsg_split.hpp, EnvDesc): one entry per LayerNorm and per split-packed Linear, checked
+    // by k_pack_h at every bind; the word it raises is the spare last word of `maxabs` (cleared with the others by k_pack_grouped)
+    DevBuf<EnvDesc> env_dev; int env_n = 0;
+    float* env_word() const { return maxabs.get() + params.size(); }
 
     // forward workspace (ensure_workspace: sized for cap_rows rows and cap_entries schedule entries)
     int cap_rows = 0, cap_entries = 0;

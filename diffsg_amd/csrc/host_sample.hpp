@@ -135,7 +135,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     else hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, s, h->fw.tvals, T);
     run_time_path(h, T, s);
     hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tpp * CG * 256, 256)), dim3(256), 0, s, cond, (const float*)nullptr, B,
-                       h->d.cond_dim, CG, h->fw.condfrag, tpp);
+                       h->d.cond_dim, CG, h->fw.condfrag, tpp, h->use_split ? h->range_flag : nullptr, kCondLimit);
     // condition embeddings of every block, once per call: cond is the same in all T steps (MSR.py:126-127)
     run_cond_embed(h, B, s);
     if (y_T) HIPCK(hipMemcpyAsync(h->fw.ywork, y_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));

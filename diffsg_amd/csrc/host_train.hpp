@@ -468,7 +468,8 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     hipLaunchKernelGGL(k_linspace_t, dim3(cdiv(T, 256)), dim3(256), 0, tstream, h->fw.tvals, T);
     run_time_path(h, T, tstream, true);
     if (time_fwd_beside) HIPCK(hipEventRecord(h->ev_tail[2], h->side_stream));
-    hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tiles * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, C, CG, h->fw.condfrag, tiles);
+    hipLaunchKernelGGL(k_cond_frag, dim3(cdiv(tiles * CG * 256, 256)), dim3(256), 0, s, cond, cond_mask, B, C, CG, h->fw.condfrag, tiles,
+                       h->use_split ? h->range_flag : nullptr, kCondLimit);
     hipLaunchKernelGGL(k_qsample, dim3(cdiv(tiles * DG * 256, 256)), dim3(256), 0, s, y, noise, h->tr.ts, sqrt_acp, sqrt_1m_acp, B, D,
                        h->tr.yt_rm, trp(h, h->tr_yt_frag), tiles);
     // the forward may run on the split-f16 kernels (they need the condition embeddings as an additive term)

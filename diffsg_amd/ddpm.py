@@ -125,19 +125,29 @@ class DDPMCore(nn.Module):
         """The output of `launch()`, which enqueues one call, under the range rule of `sample`'s `check_range`: read the range flag and,
         if it is set, launch again on the exact-float32 kernels, then restore the caller's precision mode; unchecked, only remember that
         the flag is still to be read."""
+        m = self.model
+
+        def exact():
+            prev = m.precision
+            m.set_precision("f32")
+            try:
+                return launch()
+            finally:
+                m.set_precision(prev)
+        # weights outside the split envelope are a property of the bind, known since the first query after it: such a model goes straight
+        # to the exact path (no split-f16 attempt, no second warning) until its weights change
+        if check_range and m.precision == "split_f16" and m.weights_known_outside_envelope():
+            return exact()
         out = launch()
         if not check_range:
             self._range_unchecked = True
-        elif self.model.range_exceeded():
+        elif (bits := m.range_status()):
             import warnings
-            warnings.warn(f"DDPM.{name}: activations exceeded the fp16 range of the split-f16 path; repeating the call with "
-                          "precision='f32'")
-            prev = self.model.precision
-            self.model.set_precision("f32")
-            try:
-                out = launch()
-            finally:
-                self.model.set_precision(prev)
+            why = ("the weights are outside the envelope of the split-f16 path (model.check_range() names the bound): this and every "
+                   "later call runs on the exact kernels until the weights change" if bits & 2 else
+                   "activations exceeded the fp16 range of the split-f16 path")
+            warnings.warn(f"DDPM.{name}: {why}; repeating the call with precision='f32'")
+            out = exact()
         return out
 
     def _raise_if_unchecked_call_saturated(self):

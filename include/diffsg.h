@@ -85,8 +85,18 @@ int dsg_set_renorm_hook(dsg_handle* h, double* stats3, void (*reduce)(void* user
 /* fp16 range of the split path's RAW operands (Linear shortcuts, Down/Upsample, feature_proj inputs are split without
  * normalisation; LayerNorm outputs are bounded and weights are scaled at bind time).  Every kernel that splits a raw operand
  * bounds its rows by |mean| + sqrt(M2) from the LayerNorm statistics and raises a per-handle flag above 6e4 (fp16 saturates at
- * 65504: the result would be silently wrong, not inf).  dsg_range_status synchronises the device, returns the flag in
- * *exceeded and clears it; on 1 the outputs since the last query are not to be trusted: rerun with DSG_PRECISION_F32_MFMA. */
+ * 65504: the result would be silently wrong, not inf).  The condition is such an operand too: 16 * silu(cond * mask) is split with no
+ * LayerNorm in front, and the same flag comes up where it exceeds 6e4.  dsg_range_status synchronises the device, returns the flag in
+ * *exceeded (bit DSG_RANGE_ACTIVATION) and clears it; when it is set the outputs since the last query are not to be trusted: rerun with
+ * DSG_PRECISION_F32_MFMA.
+ * Bit DSG_RANGE_WEIGHTS reports the bound WEIGHTS instead: dsg_bind_weights computes (on the device, no synchronise), for every LayerNorm
+ * in front of a split product, 16 * (max|gamma| * sqrt(features) + max|beta|) -- the bound of its SiLU output at the activation scale --
+ * and max|W| of every split-packed Linear; the bit is set while the first exceeds 6e4 or the second reaches 2^21 (the per-layer weight
+ * scale is clamped there) and the handle is in DSG_PRECISION_SPLIT_F16.  It is not cleared by the query: the next dsg_bind_weights
+ * recomputes it.  A non-zero *exceeded means "use DSG_PRECISION_F32_MFMA", for this call or, with DSG_RANGE_WEIGHTS, for these
+ * weights. */
+#define DSG_RANGE_ACTIVATION 1
+#define DSG_RANGE_WEIGHTS 2
 int dsg_range_status(dsg_handle* h, int* exceeded);
 /* The same query behind the work already enqueued on ONE stream: synchronises `stream` only (other streams of the device keep running;
  * the default DDPM.sample() stalled every stream of the device once per call) and reads / clears the flag stream-ordered. */
