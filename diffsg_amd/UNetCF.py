@@ -151,7 +151,10 @@ class _Native:
         self.step_grid = None             # (handle, plan, its coef on the device), or None: dsg_set_step_grid
         self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
         self.step_guidance = None         # (handle, the weights as a tuple of floats, their tensor, its version), or None: dsg_set_step_guidance
-        self.env_out_key = None           # the `bound_key` whose weights a range query found outside the split envelope, or None
+        # ... and DDPM's training calls (setting either moves dsg_generation: a captured step is captured again)
+        self.train_law = None             # (handle, the timesteps.TrainLaw), or None: dsg_set_train_law
+        self.train_report = None          # (handle, sq tensor, rows tensor), or None: dsg_set_train_report
+        self.env_out_key = None          # the `bound_key` whose weights a range query found outside the split envelope, or None
         _NATIVES.add(self)
 
     def __deepcopy__(self, memo):

@@ -204,6 +204,57 @@ int dsg_set_step_guidance(dsg_handle* h, const float* g_host, int n) {
     return 0;
 }
 
+int dsg_set_train_law(dsg_handle* h, const unsigned* cdf24_host, const float* weight_host, int T) {
+    if (!h) return fail("null handle");
+    if (T < 0) return fail("dsg_set_train_law: T = %d is negative", T);
+    if ((!cdf24_host && !weight_host) || T == 0) {     // nothing is overwritten: an enqueued step keeps reading the buffers
+        if (h->law_T) { h->law_T = 0; h->law_has_cdf = h->law_has_w = false; ++h->generation; }
+        return 0;
+    }
+    if (cdf24_host) {
+        for (int k = 1; k < T; ++k)
+            if (cdf24_host[k] < cdf24_host[k - 1])
+                return fail("dsg_set_train_law: the CDF decreases at step %d (%u after %u)", k, cdf24_host[k], cdf24_host[k - 1]);
+        if (cdf24_host[T - 1] != (1u << 24))
+            return fail("dsg_set_train_law: the last CDF entry is %u, not 2^24 = %u", cdf24_host[T - 1], 1u << 24);
+    }
+    if (weight_host)
+        for (int k = 0; k < T; ++k)
+            if (!(weight_host[k] >= 0.f && weight_host[k] <= 3.402823466e38f))     // NaN fails the first comparison, +inf the second
+                return fail("dsg_set_train_law: weight %d is %g: the weights are finite and >= 0", k, (double)weight_host[k]);
+    DeviceGuard dg(h);
+    // an enqueued step may still read the old law
+    HIPCK(hipDeviceSynchronize());
+    if (T > h->law_cap) {       // the new buffers first: a failed allocation leaves the law the handle holds as it was
+        DevBuf<unsigned> c;
+        DevBuf<float> w;
+        HIPCK(c.alloc((size_t)T));
+        HIPCK(w.alloc((size_t)T));
+        h->law_cdf = std::move(c); h->law_w = std::move(w);
+        h->law_cap = T;
+    }
+    if (cdf24_host) HIPCK(hipMemcpy(h->law_cdf, cdf24_host, (size_t)T * sizeof(unsigned), hipMemcpyHostToDevice));
+    if (weight_host) HIPCK(hipMemcpy(h->law_w, weight_host, (size_t)T * sizeof(float), hipMemcpyHostToDevice));
+    h->law_T = T; h->law_has_cdf = cdf24_host != nullptr; h->law_has_w = weight_host != nullptr;
+    ++h->generation;            // a captured step holds the kernel forms and the buffers of the law it was captured under
+    return 0;
+}
+
+int dsg_set_train_report(dsg_handle* h, double* sq_dev, long long* rows_dev, int T) {
+    if (!h) return fail("null handle");
+    if (T < 0) return fail("dsg_set_train_report: T = %d is negative", T);
+    if (!sq_dev || T == 0) {
+        if (h->rep_T) { h->rep_T = 0; h->rep_sq = nullptr; h->rep_rows = nullptr; ++h->generation; }
+        return 0;
+    }
+    if (!rows_dev) return fail("dsg_set_train_report: sq_dev without rows_dev");
+    if (h->rep_T != T || h->rep_sq != sq_dev || h->rep_rows != rows_dev) {
+        h->rep_sq = sq_dev; h->rep_rows = rows_dev; h->rep_T = T;
+        ++h->generation;        // a captured step holds the report launch and the caller's two addresses
+    }
+    return 0;
+}
+
 int dsg_set_chunk_variants(dsg_handle* h, const float* omega_host, const int* renorm_host, const int* table_host, int chunks, int tables) {
     if (!h) return fail("null handle");
     if (chunks < 0) return fail("dsg_set_chunk_variants: chunks = %d is negative", chunks);
@@ -365,6 +416,7 @@ int dsg_train_step(dsg_handle* h, const float* y, const float* cond, const int* 
     if (B < 1 || T < 1) return fail("B and T must be >= 1");
     if (!y || !cond || !ts || !noise || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out)
         return fail("dsg_train_step: null pointer argument");
+    if (train_law_refused(h, "dsg_train_step", T)) return 1;
     if (ensure_train_workspace(h, B, T)) return 1;
     return train_step_impl(h, y, cond, ts, noise, cond_mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
 }
@@ -387,17 +439,15 @@ int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, 
     if (check_bound(h)) return 1;
     if (B < 1 || T < 1) return fail("B and T must be >= 1");
     if (!y || !cond || !call_dev || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded_dyn: null pointer argument");
+    if (train_law_refused(h, "dsg_train_step_seeded_dyn", T)) return 1;
     if (ensure_train_workspace(h, B, T)) return 1;
     const int D = h->d.input_dim;
     if (ensure_train_draws(h)) return 1;
-    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
     hipStream_t s = (hipStream_t)stream;
     // every refusal of train_step_impl comes FIRST: a refused call enqueues nothing, so *call_dev stays where it was (the tables built here
     // are the ones train_step_impl then finds current)
     if (train_shape_refused(h) || build_train_descs(h, B, T, s)) return 1;
-    hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, s, h->tr.ts, h->tr.noise, h->tr.mask, B, D, T, keep_prob, seed, 0u,
-                       (const unsigned long long*)call_dev);
+    launch_train_draws(h, B, D, T, keep_prob, seed, 0u, (const unsigned long long*)call_dev, s);
     hipLaunchKernelGGL(k_bump_u64, dim3(1), dim3(64), 0, s, call_dev);
     HIPCK(hipGetLastError());
     return train_step_impl(h, y, cond, h->tr.ts, h->tr.noise, h->tr.mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, s);
@@ -409,11 +459,16 @@ int dsg_train_step_seeded(dsg_handle* h, const float* y, const float* cond, unsi
     if (check_bound(h)) return 1;
     if (B < 1 || T < 1) return fail("B and T must be >= 1");
     if (!y || !cond || !sqrt_acp || !sqrt_1m_acp || !grads_flat || !loss_out) return fail("dsg_train_step_seeded: null pointer argument");
+    if (train_law_refused(h, "dsg_train_step_seeded", T)) return 1;
     if (ensure_train_workspace(h, B, T)) return 1;
     const int D = h->d.input_dim;
     if (ensure_train_draws(h)) return 1;
     // ts goes straight into the workspace copy the step reads (train_step_impl skips its own copy when handed that pointer)
-    if (dsg_train_draws(seed, call, T, keep_prob, B, D, h->tr.ts, h->tr.noise, h->tr.mask, stream)) return 1;
+    if (h->law_T && h->law_has_cdf) {       // the law's draw (dsg_set_train_law): the same refusal, then the second kernel
+        if (call >> 30) return fail("dsg_train_draws: call counter out of range (2^30)");
+        launch_train_draws(h, B, D, T, keep_prob, seed, (unsigned)call, nullptr, (hipStream_t)stream);
+        HIPCK(hipGetLastError());
+    } else if (dsg_train_draws(seed, call, T, keep_prob, B, D, h->tr.ts, h->tr.noise, h->tr.mask, stream)) return 1;
     return train_step_impl(h, y, cond, h->tr.ts, h->tr.noise, h->tr.mask, sqrt_acp, sqrt_1m_acp, T, grads_flat, loss_out, B, (hipStream_t)stream);
 }
 

@@ -108,6 +108,97 @@ __global__ __launch_bounds__(256) void k_loss_final(const double* __restrict__ p
 }
 
 // ---------------------------------------------------------------------------------------------
+// Training on a timestep law (dsg_set_train_law, dsg_set_train_report).  Second kernels beside the three above: a handle
+// that holds neither setting launches exactly what it launched before.
+// ---------------------------------------------------------------------------------------------
+// k_train_draws with ts drawn from an integer CDF on the 24-bit grid: the SAME Philox word as the uniform draw (counter (i4, 4*call + 1),
+// lane p, u24 = r >> 8), ts = #{k : cdf24[k] <= u24} (upper bound, integers only).  cdf24[T-1] == 2^24 > u24, so ts <= T-1; a step whose
+// interval is empty (cdf24[k] == cdf24[k-1]) is never drawn.  Noise and mask: the expressions of k_train_draws.
+__global__ void k_train_draws_law(int* __restrict__ ts, float* __restrict__ noise, float* __restrict__ mask, int B, int D, int T, float keep,
+                                  unsigned long long seed, unsigned call_v, const unsigned long long* __restrict__ call_ptr,
+                                  const unsigned* __restrict__ cdf24) {
+    const unsigned call = call_ptr ? (unsigned)*call_ptr : call_v;
+    const size_t n = (size_t)B * D, n4 = (n + 3) / 4, b4 = ((size_t)B + 3) / 4;
+    for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
+        if (noise) {
+            float zz[4];
+            normal4(seed, 4u * call, i4, zz);
+            for (int p = 0; p < 4; ++p)
+                if (i4 * 4 + p < n) noise[i4 * 4 + p] = zz[p];
+        }
+        if (i4 < b4) {
+            uint32_t r[4], q[4];
+            philox4x32_10((uint32_t)i4, (uint32_t)(i4 >> 32), 4u * call + 1u, 0x5eedu, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+            philox4x32_10((uint32_t)i4, (uint32_t)(i4 >> 32), 4u * call + 2u, 0x5eedu, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+            for (int p = 0; p < 4; ++p) {
+                const size_t row = i4 * 4 + p;
+                if (row >= (size_t)B) break;
+                if (ts) {
+                    const unsigned u24 = r[p] >> 8;
+                    int lo = 0, hi = T;                    // first k with cdf24[k] > u24
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (cdf24[mid] <= u24) lo = mid + 1; else hi = mid;
+                    }
+                    ts[row] = lo < T ? lo : T - 1;
+                }
+                if (mask) mask[row] = ((q[p] >> 8) * (1.0f / 16777216.0f)) < keep ? 1.0f : 0.0f;
+            }
+        }
+    }
+}
+
+// k_loss_grad with a weight per timestep: loss = sum_r w[ts_r] sum_f d^2 / (B*D), d_eps = (d * 2/(B*D)) * w[ts_r].  Same grid, same
+// assignment and the same float64 partials as k_loss_grad; with every weight 1.0f the bits of k_loss_grad.
+__global__ __launch_bounds__(256) void k_loss_grad_w(const float* __restrict__ eps, const float* __restrict__ noise, int nrows, int D,
+                                                     float* __restrict__ deps_frag, int ntiles, double* __restrict__ part,
+                                                     const int* __restrict__ ts, const float* __restrict__ wt) {
+    __shared__ double sm[4];
+    const int DG = (D + 7) / 8;
+    const size_t total = (size_t)ntiles * DG * 256;
+    const float scale = 2.0f / ((float)nrows * (float)D);
+    double s = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int p = idx & 3, lane = (idx >> 2) & 63;
+        const size_t tg = idx >> 8;
+        const int g = tg % DG, tile = tg / DG;
+        const int row = tile * 32 + (lane & 31), f = 8 * g + 4 * (lane >> 5) + p;
+        float v = 0.f;
+        if (row < nrows && f < D) {
+            const float w = wt[ts[row]];
+            const float d = eps[(size_t)row * D + f] - noise[(size_t)row * D + f];
+            s += (double)w * ((double)d * (double)d);
+            v = __fmul_rn(__fmul_rn(d, scale), w);
+        }
+        deps_frag[idx] = v;
+    }
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// dsg_set_train_report: block t adds the UNWEIGHTED sum over the rows with ts == t of sum_f (eps_hat - eps)^2 (float64) to sq[t] and their
+// number to rows[t].  One block per timestep, a fixed assignment of rows to threads and a fixed tree (as k_loss_final), and ONE writer
+// per entry: deterministic run to run, no atomics.  The buffers accumulate across steps (stream-ordered read-modify-write).
+__global__ __launch_bounds__(256) void k_loss_report(const float* __restrict__ eps, const float* __restrict__ noise, const int* __restrict__ ts,
+                                                     int nrows, int D, double* __restrict__ sq, long long* __restrict__ rows) {
+    __shared__ double sm[4];
+    const int t = blockIdx.x;
+    double s = 0.0, c = 0.0;          // the count as a double: exact below 2^53
+    for (int row = threadIdx.x; row < nrows; row += 256) {
+        if (ts[row] != t) continue;
+        const float* e = eps + (size_t)row * D;
+        const float* z = noise + (size_t)row * D;
+        double a = 0.0;
+        for (int f = 0; f < D; ++f) { const float d = e[f] - z[f]; a += (double)d * (double)d; }
+        s += a;
+        c += 1.0;
+    }
+    s = block_sum(s, sm);
+    c = block_sum(c, sm);
+    if (threadIdx.x == 0 && c > 0.0) { sq[t] += s; rows[t] += (long long)c; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Column sums over the 32 rows of a tile, in registers (bias and LayerNorm gamma/beta gradients of the residual blocks).
 // v[r], r < R (R a power of two <= 32), holds one value per row (lane & 31) for R different columns.  Afterwards lane l
 // returns the sum over the 32 lanes of its half of column l & (R - 1).  Butterfly: each level halves the registers -- the

@@ -165,7 +165,8 @@ struct dsg_handle {
     // dsg_generation: moves whenever something a captured training step (train.StepGraph) may hold stops being valid -- a workspace is
     // freed (free_workspace, free_train_workspace), the launch plan changes (precision mode, launch policy, an option that takes another
     // value), or the per-batch-size tables of the training step are rewritten for another batch (build_train_descs, the narrow run's
-    // training table).  Host only; never reset.
+    // training table), or the train law or the train report is set, replaced or removed (dsg_set_train_law, dsg_set_train_report: the
+    // captured launches hold the kernel forms chosen under them and their buffers).  Host only; never reset.
     unsigned long long generation = 0;
 
     // fp16-split path (dsg_split.hpp): wide blocks of the sampling loop
@@ -283,6 +284,13 @@ struct dsg_handle {
     int var_chunks = 0, var_tables = 1; bool var_has_renorm = false, var_has_table = false;
     std::vector<int> var_renorm_host;            // the counts, for the checks a call makes before it enqueues anything
     DevBuf<VarParams> var_call;
+
+    // dsg_set_train_law: the integer CDF and the loss weight per timestep of the training steps; law_T == 0: none held.  The buffers only
+    // grow and are kept when the law is removed.  A captured training step holds their addresses and the kernel forms chosen under the
+    // law, so setting, changing or removing it moves `generation`.
+    DevBuf<unsigned> law_cdf; DevBuf<float> law_w; int law_T = 0, law_cap = 0; bool law_has_cdf = false, law_has_w = false;
+    // dsg_set_train_report: the caller's per-timestep accumulators (device, NOT owned); rep_T == 0: none held.  Moves `generation` too.
+    double* rep_sq = nullptr; long long* rep_rows = nullptr; int rep_T = 0;
 
     // training workspace
     size_t tr_per_tile = 0;      // floats per tile

@@ -442,6 +442,28 @@ int train_shape_refused(dsg_handle* h) {
     return 0;
 }
 
+// a training call whose T is not the one of the law or report the handle holds (dsg_set_train_law, dsg_set_train_report): refused by
+// the entry points before anything is enqueued -- the kernels index [T]-sized buffers with ts
+int train_law_refused(const dsg_handle* h, const char* who, int T) {
+    if (h->law_T && T != h->law_T)
+        return fail("%s: the handle's train law (dsg_set_train_law) has T = %d, the call has T = %d", who, h->law_T, T);
+    if (h->rep_T && T != h->rep_T)
+        return fail("%s: the handle's train report (dsg_set_train_report) has T = %d, the call has T = %d", who, h->rep_T, T);
+    return 0;
+}
+
+// the draws of a seeded step: k_train_draws, or under a law with a CDF its second kernel (same grid, same noise and mask)
+void launch_train_draws(const dsg_handle* h, int B, int D, int T, float keep_prob, unsigned long long seed, unsigned call_v,
+                        const unsigned long long* call_ptr, hipStream_t s) {
+    const size_t blocks = (((size_t)B * D + 3) / 4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    if (h->law_T && h->law_has_cdf)
+        hipLaunchKernelGGL(k_train_draws_law, dim3(grid), dim3(256), 0, s, h->tr.ts, h->tr.noise, h->tr.mask, B, D, T, keep_prob, seed, call_v,
+                           call_ptr, (const unsigned*)h->law_cdf);
+    else
+        hipLaunchKernelGGL(k_train_draws, dim3(grid), dim3(256), 0, s, h->tr.ts, h->tr.noise, h->tr.mask, B, D, T, keep_prob, seed, call_v, call_ptr);
+}
+
 int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int* ts, const float* noise, const float* cond_mask,
                     const float* sqrt_acp, const float* sqrt_1m_acp, int T, float* grads_flat, float* loss_out, int B, hipStream_t s) {
     // every shape the backward kernels cannot take is refused HERE, before anything is enqueued (the same check in the middle of
@@ -478,8 +500,14 @@ int train_step_impl(dsg_handle* h, const float* y, const float* cond, const int*
     if (prepare_fused(h, c, s)) return 1;
     if (time_fwd_beside) HIPCK(hipStreamWaitEvent(s, h->ev_tail[2], 0));   // the time table
     run_unet(h, c, s);
-    hipLaunchKernelGGL(k_loss_grad, dim3(kRedBlocks), dim3(256), 0, s, h->fw.eps, noise, B, D, trp(h, h->tr_deps), tiles, h->red);
+    if (h->law_T && h->law_has_w)      // a weight per timestep (dsg_set_train_law): the second kernel; without one, today's launch
+        hipLaunchKernelGGL(k_loss_grad_w, dim3(kRedBlocks), dim3(256), 0, s, h->fw.eps, noise, B, D, trp(h, h->tr_deps), tiles, h->red,
+                           (const int*)h->tr.ts, (const float*)h->law_w);
+    else
+        hipLaunchKernelGGL(k_loss_grad, dim3(kRedBlocks), dim3(256), 0, s, h->fw.eps, noise, B, D, trp(h, h->tr_deps), tiles, h->red);
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(256), 0, s, h->red, kRedBlocks, (double)B * (double)D, loss_out);
+    if (h->rep_T)                      // dsg_set_train_report: one extra small launch, only while a report is held
+        hipLaunchKernelGGL(k_loss_report, dim3(h->rep_T), dim3(256), 0, s, h->fw.eps, noise, (const int*)h->tr.ts, B, D, h->rep_sq, h->rep_rows);
 
     // ---- backward: activation gradients in reverse operator order
     mark(1);

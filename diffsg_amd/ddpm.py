@@ -552,6 +552,7 @@ class DDPMCore(nn.Module):
         self._raise_if_unchecked_call_saturated()
         hd = self.model.native_handle()
         B, dev = y.shape[0], y.device
+        self._use_train_settings(hd, dev)
         if self.device_draws is not None and ts is None and noise is None and cond_mask is None:
             return self._forward_device_draws(hd, y, cond)
         if ts is None or noise is None or cond_mask is None:
@@ -565,7 +566,12 @@ class DDPMCore(nn.Module):
                 side = self._draw_stream = torch.cuda.Stream(dev)
             with torch.cuda.stream(side):
                 if ts is None:
-                    ts = torch.randint(low=0, high=self.T, size=(1, B), device=dev)
+                    if self.train_law is not None and self.train_law.cdf24 is not None:
+                        # the law's draw in the place of the reference's randint(0, T): the library's integer rule on a 24-bit draw
+                        u24 = torch.randint(low=0, high=2 ** 24, size=(1, B), device=dev)
+                        ts = torch.searchsorted(self._law_cdf_on(dev), u24, right=True)
+                    else:
+                        ts = torch.randint(low=0, high=self.T, size=(1, B), device=dev)
                 if noise is None:
                     noise = torch.randn_like(y)
                 if cond_mask is None:
@@ -606,8 +612,121 @@ class DDPMCore(nn.Module):
     #: deterministic run to run).
     train_split_min_rows = 65536
 
+    #: A `timesteps.TrainLaw`, or None (the reference's rule: ts ~ U{0..T-1}, unweighted mean).  While it is set every training step on
+    #: this object draws ts from the law's CDF (device draws: the library's integer rule; torch's generator: the same upper bound of
+    #: `randint(0, 2**24)`) and weights each row's squared error with w[ts]; DESIGN.md 17.  While a law or a loss report
+    #: (`loss_report`) is held NO batch runs as two halves, whatever `train_split_min_rows` says: a split batch draws through the
+    #: handle-free dsg_train_draws, which knows no law, and the two halves would race on the report's buffers.
+    train_law = None
+
+    def _law_held(self):
+        law = self.train_law
+        return law is not None and (law.cdf24 is not None or law.w is not None)
+
     def _splits(self, B):
+        if self._law_held() or getattr(self, "_report", None) is not None:
+            return False
         return self.train_split_min_rows is not None and B >= self.train_split_min_rows and B >= 128
+
+    def _native_of(self, hd):
+        m = self.model
+        for nat in [m._native] + list(m.__dict__.get("_twins", {}).values()):
+            if nat.handle == hd:
+                return nat
+        raise RuntimeError("DDPM: not a handle of this model")
+
+    def _use_law(self, hd, law, dev):
+        """Make handle `hd` hold `law` (None, or a law without arrays: none).  What the handle holds is remembered beside it, as
+        `_use_plan` does: a repeated step sets nothing (setting a law synchronises the device and moves dsg_generation)."""
+        import ctypes
+        nat = self._native_of(hd)
+        held = nat.train_law
+        if held is not None and held[0] != hd:
+            held = None
+        if law is not None and law.cdf24 is None and law.w is None:
+            law = None
+        if law is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_train_law(hd, None, None, 0))
+                nat.train_law = None
+            return
+        if held is not None and held[1] is law:
+            return
+        if law.T != self.T:
+            raise ValueError(f"train_law is a law over T = {law.T} timesteps, the model has T = {self.T}")
+        cdf = None if law.cdf24 is None else (ctypes.c_uint * law.T)(*[int(v) for v in law.cdf24])
+        w = None if law.w is None else (ctypes.c_float * law.T)(*[float(v) for v in law.w])
+        with torch.cuda.device(dev):          # a refused call leaves what the handle holds, and this record of it, unchanged
+            _lib.check(_lib.lib().dsg_set_train_law(hd, cdf, w, law.T))
+        nat.train_law = (hd, law)
+
+    def _use_report(self, hd, dev):
+        """Make handle `hd` add to the buffers of `loss_report` (none: remove the report); remembered beside the handle."""
+        nat = self._native_of(hd)
+        held = nat.train_report
+        if held is not None and held[0] != hd:
+            held = None
+        rep = getattr(self, "_report", None)
+        if rep is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_train_report(hd, None, None, 0))
+                nat.train_report = None
+            return
+        if not rep or rep[0].device != dev:    # turned on before the model reached its device: the buffers are made at the first step
+            rep = self._report = (torch.zeros(self.T, dtype=torch.float64, device=dev), torch.zeros(self.T, dtype=torch.int64, device=dev))
+        if held is not None and held[1] is rep[0] and held[2] is rep[1]:
+            return
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().dsg_set_train_report(hd, _lib.ptr(rep[0]), _lib.ptr(rep[1]), self.T))
+        nat.train_report = (hd, rep[0], rep[1])
+
+    def _law_cdf_on(self, dev):
+        """The law's CDF as an int64 tensor on `dev` (the host-generator path's upper bound), cached per law."""
+        law, c = self.train_law, getattr(self, "_law_cdf_dev", None)
+        if c is None or c[0] is not law or c[1].device != dev:
+            c = self._law_cdf_dev = (law, torch.tensor(law.cdf24.tolist(), dtype=torch.int64, device=dev))
+        return c[1]
+
+    def _use_train_settings(self, hd, dev):
+        self._use_law(hd, self.train_law, dev)
+        self._use_report(hd, dev)
+
+    def _sync_train_settings(self):
+        """The law and the report on every handle of the model that exists (train.StepGraph.step: a replay does not pass through
+        `forward`, and a change must move dsg_generation before the capture is judged)."""
+        m = self.model
+        for nat in [m._native] + list(m.__dict__.get("_twins", {}).values()):
+            if nat.handle:
+                self._use_train_settings(nat.handle, next(m.parameters()).device)
+
+    def loss_report(self, on=True):
+        """Turn the loss by timestep on (two device buffers: float64 [T] sums of the UNWEIGHTED squared error and int64 [T] row counts,
+        added to by every training step, stream-ordered, with no synchronise) or off.  Read with `read_loss_report`."""
+        if not on:
+            self._report = None
+        elif getattr(self, "_report", None) is None:
+            dev = next(self.model.parameters()).device
+            self._report = () if dev.type != "cuda" else (torch.zeros(self.T, dtype=torch.float64, device=dev),
+                                                          torch.zeros(self.T, dtype=torch.int64, device=dev))
+        if not on:
+            self._sync_train_settings()       # the handles stop writing before the buffers can go
+
+    def read_loss_report(self, reset=True):
+        """(mean_sq [T] float64, rows [T] int64) on the host: mean_sq[t] = (sum over the rows drawn at t of sum_f (eps_hat - eps)^2) /
+        (rows[t] * D) since the last reset, NaN where no row was drawn.  One synchronise.  `reset`: zero the buffers behind the read."""
+        rep = getattr(self, "_report", None)
+        if rep is None:
+            raise RuntimeError("DDPM.read_loss_report: no report is on (loss_report(True))")
+        if not rep:                            # on, and no step yet
+            return torch.full((self.T,), float("nan"), dtype=torch.float64), torch.zeros(self.T, dtype=torch.int64)
+        both = torch.stack((rep[0], rep[1].to(torch.float64))).cpu()      # one copy, one synchronise (counts below 2^53 are exact)
+        if reset:
+            rep[0].zero_()
+            rep[1].zero_()
+        sq, rows = both[0], both[1].to(torch.int64)
+        D = self.model.cfg["input_dim"]
+        mean = torch.where(rows > 0, sq / (rows.to(torch.float64) * D).clamp(min=1.0), torch.full_like(sq, float("nan")))
+        return mean, rows
 
     def _run_halves(self, launch, hd, B, dev, work, inputs):
         """Enqueue the fused step for rows [0, B): one launch on the caller's stream, or two halves -- rows [0, nA) on the caller's
@@ -627,6 +746,7 @@ class DDPMCore(nn.Module):
             side.wait_stream(main)                      # the inputs (and the optimizer's last update) are ready for the side stream
             with torch.cuda.stream(side):
                 hb = self.model.native_handle(twin=1)   # binds (re-packs) on the side stream
+                self._use_train_settings(hb, dev)       # (a split batch holds neither: this removes what an earlier step left there)
                 launch(hb, nA, B, work_b, losses[1:])
             launch(hd, 0, nA, work, losses[:1])
             main.wait_stream(side)
@@ -696,6 +816,7 @@ class DDPMCore(nn.Module):
             def launch(handle, lo, hi, wk, ls):
                 if twin:
                     handle = self.model.native_handle(twin=twin)
+                    self._use_train_settings(handle, dev)
                 if dyn is not None:
                     _lib.check(L.dsg_train_step_seeded_dyn(handle, _lib.ptr(y32[lo:hi]), _lib.ptr(c32[lo:hi]), seed, _lib.ptr(dyn),
                                                            float(1.0 - self.uncond_prob), sa, sb, self.T, _lib.ptr(wk), _lib.ptr(ls), hi - lo,

@@ -80,6 +80,8 @@ def train(build, X_train, Y_train, lr, milestones, epochs, use_ema, warmup_epoch
     if dev is None:
         dev = device()                      # raises: no CPU path
     diffusion_model = build(dev)
+    from . import timesteps
+    timesteps.apply_active(diffusion_model)     # the options of an enclosing timesteps.training(law=..., report=...); nothing outside one
     diffusion_model.apply(init_weights)
     diffusion_model.to(dev)
     sync_replicas(diffusion_model)          # data parallel: rank 0's initial weights everywhere (no-op for one process)

@@ -225,6 +225,9 @@ class StepGraph:
     def _before_step(self):
         if self.ddpm._draw_calls >> 30:
             raise RuntimeError("StepGraph: the call counter of the device-side draws is out of range (2^30)")
+        # a replay does not pass through DDPM.forward: a law or a report set, changed or removed since the last step reaches the handles
+        # here, and moves dsg_generation (the capture is then dropped and made again behind an eager step); nothing when unchanged
+        self.ddpm._sync_train_settings()
         lr = float(self.opt.param_groups[0]["lr"])
         if getattr(self.opt, "_dyn", None) is not None and lr != self._lr_host:
             self.opt._dyn["lr"].fill_(lr)      # MultiStepLR moved it (once per milestone): a stream-ordered 8-byte write
@@ -439,6 +442,22 @@ class _BatchesAsLoader:
         return (self.batches.take(idx) for idx in self.batches.epoch(self._epoch))
 
 
+def _read_loss_by_t(diffusion_model, epoch):
+    """With a loss report on (`DDPM.loss_report`): read and zero it right behind the epoch's own synchronise, keep the epoch's mean squared
+    error per timestep in `diffusion_model.loss_by_t` (a list, one float64 [T] tensor per epoch, NaN where no row was drawn; the row counts
+    in `loss_rows_by_t`) and return the second log line of the epoch, which goes out after the pinned `Epoch: e, Loss: ...` line.  None
+    without a report."""
+    if getattr(diffusion_model, "_report", None) is None:
+        return None
+    mean_sq, rows = diffusion_model.read_loss_report(reset=True)
+    if not isinstance(getattr(diffusion_model, "loss_by_t", None), list):
+        diffusion_model.loss_by_t = []
+        diffusion_model.loss_rows_by_t = []
+    diffusion_model.loss_by_t.append(mean_sq)
+    diffusion_model.loss_rows_by_t.append(rows)
+    return f"Epoch: {epoch}, Loss by timestep: " + " ".join(f"{v:.4g}" for v in mean_sq.tolist())
+
+
 def _run_epochs_graph(diffusion_model, batches, optimizer, scheduler, epochs, use_ema, warmup_epoch, device, log):
     """`run_epochs(graph=True)`: every full batch is `DeviceBatches.fill` into static buffers and one `StepGraph.step()`; the ragged last
     batch one eager step of the same sequence (`StepGraph.step_on`)."""
@@ -467,11 +486,14 @@ def _run_epochs_graph(diffusion_model, batches, optimizer, scheduler, epochs, us
                 epoch_rows += idx.numel()
                 ema_step_cnt += 1
             epoch_loss = epoch_sum.item()       # the epoch's one synchronise
+            by_t = _read_loss_by_t(diffusion_model, epoch)      # behind that synchronise; one small copy, no further wait
             # one health check per epoch, on the sum (a NaN or inf of any step stays in it) and on the sticky fp16 range flag: an invalid
             # step is reported at the END of its epoch, after the steps that followed it
             step_health(diffusion_model, epoch_loss, device, 1,
                         where=f"epoch {epoch} (graph=True: checked once, at the end of the epoch, over all its steps)")
             log(f"Epoch: {epoch}, Loss: {epoch_loss / epoch_rows}")
+            if by_t is not None:
+                log(by_t)
             scheduler.step()
     finally:
         sg.close()
@@ -541,5 +563,8 @@ def run_epochs(diffusion_model, loader, optimizer, scheduler, epochs, use_ema, w
             ema_step_cnt += 1
         # the reference prints (sum of batch-mean losses) / (row count), MSR.py:233 -- reproduced as is
         log(f"Epoch: {epoch}, Loss: {epoch_loss / epoch_rows}")
+        by_t = _read_loss_by_t(diffusion_model, epoch)
+        if by_t is not None:
+            log(by_t)
         scheduler.step()
     return diffusion_model

@@ -152,7 +152,12 @@ int dsg_reserve(dsg_handle* h, int max_rows, int max_entries);
  *   - the launch plan changes: dsg_set_precision, dsg_set_launch_policy, and dsg_set_option when the option takes ANOTHER value (setting
  *     what is already held moves nothing);
  *   - the per-batch-size tables of the training step are rewritten in place: a training step of another batch size, T or precision mode on
- *     this handle (the captured launches would read the other step's tables).
+ *     this handle (the captured launches would read the other step's tables);
+ *   - the train law or the train report changes: dsg_set_train_law and dsg_set_train_report, setting, replacing or removing (removing what
+ *     is not held moves nothing; setting the report buffers already held moves nothing).  Of the two designs a captured step could survive
+ *     such a change by, this is the second: the captured launches hold the kernel forms chosen under the law (k_train_draws or its law
+ *     form, k_loss_grad or its weighted form, the report launch or none) and the buffer addresses, so the holder re-captures; the step
+ *     after the change runs eagerly and is the eager step bit for bit.
  * dsg_set_step_grid, dsg_set_chunk_variants, dsg_set_renorm_hook, dsg_bind_weights and sampling calls that fit the workspace do not touch
  * the training step and do not move it.  A holder of a captured step records the value after the capture and, when it has moved, runs
  * the step eagerly (which re-creates what is missing) and captures again.  Never decreases; 0 for a null handle. */
@@ -305,6 +310,35 @@ int dsg_train_step_seeded_dyn(dsg_handle* h, const float* y, const float* cond, 
                               int B, void* stream);
 int dsg_adam_step_dyn(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long long n, const double* lr_dev, double beta1, double beta2,
                       double eps, double weight_decay, int maximize, float* step_dev, void* stream);
+
+/* Training on a timestep law: a non-uniform draw of ts and a loss weight per timestep, per handle.
+ *   cdf24_host   HOST array [T]: a non-decreasing integer CDF on the 24-bit grid, last entry exactly 2^24; NULL: the uniform draw, exactly
+ *                the expression of dsg_train_draws;
+ *   weight_host  HOST array [T] of finite floats >= 0; NULL: every weight 1.
+ * Both NULL, or T == 0, removes the law.  Refused under this function's name: T < 0, a decreasing CDF, a last entry != 2^24, a negative or
+ * non-finite weight.  While a law is held
+ *   - dsg_train_step_seeded and dsg_train_step_seeded_dyn take the Philox word the uniform draw uses (counter (i4, 4 * call + 1), lane p,
+ *     u24 = r >> 8) and set ts = #{k : cdf24[k] <= u24}: an upper bound in integer arithmetic, which the host can restate exactly.  A
+ *     timestep with an empty interval (cdf24[k] == cdf24[k-1], or cdf24[0] == 0) is never drawn.  Noise and mask draws are untouched;
+ *   - EVERY training step on the handle (dsg_train_step with the caller's ts included) computes
+ *         loss = sum_r w[ts_r] sum_f (eps_hat - eps)^2 / (B * D)
+ *     (the denominator and the fixed order of the float64 partial sums unchanged) and seeds the backward with
+ *     d_eps = (d * 2 / (B * D)) * w[ts_r]: with every weight 1.0f these are the bits of the step without a law;
+ *   - a training call whose T differs from the law's fails before anything is enqueued and names both numbers; on the _dyn path *call_dev
+ *     stays where it was.
+ * dsg_unet_forward, dsg_train_draws (it takes no handle) and the sampling calls ignore the law.  The arrays are copied into device buffers
+ * the handle owns.  Like the other settings calls this one takes no stream: it selects the handle's device itself and synchronises that
+ * device before it overwrites the buffers; removing the law overwrites nothing and does not synchronise.  Moves dsg_generation. */
+int dsg_set_train_law(dsg_handle* h, const unsigned* cdf24_host, const float* weight_host, int T);
+
+/* Loss by timestep: sq_dev [T] (float64) and rows_dev [T] (int64) are the CALLER's device buffers, borrowed until the report is removed
+ * (sq_dev == NULL or T == 0).  While it is held every training step on the handle adds, stream-ordered and per timestep t, the UNWEIGHTED
+ * sum over the rows with ts_r == t of sum_f (eps_hat - eps)^2 to sq_dev[t] and the number of such rows to rows_dev[t]: one extra small
+ * launch per step.  The buffers accumulate across steps (replays of a captured step keep adding); the caller reads and zeroes them.  One
+ * block per timestep with a fixed assignment of rows to threads, a fixed tree and one writer per entry: deterministic run to run, no
+ * floating-point atomics.  A training call whose T differs from the report's fails before anything is enqueued.  Refused: T < 0, sq_dev
+ * without rows_dev.  No stream; nothing of the handle's is overwritten, so nothing synchronises.  Moves dsg_generation. */
+int dsg_set_train_report(dsg_handle* h, double* sq_dev, long long* rows_dev, int T);
 
 /* avg = decay*avg + one_minus_decay*p over n floats   (ddpm_opt/ema.py:11-12). */
 int dsg_ema_update(float* avg, const float* p, float decay, float one_minus_decay, long long n, void* stream);
