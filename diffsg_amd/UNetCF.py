@@ -151,6 +151,7 @@ class _Native:
         self.step_grid = None             # (handle, plan, its coef on the device), or None: dsg_set_step_grid
         self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
         self.step_guidance = None         # (handle, the weights as a tuple of floats, their tensor, its version), or None: dsg_set_step_guidance
+        self.step_history = None          # (handle, the rows as a tuple of floats, their tensor, its version), or None: dsg_set_step_history
         # ... and DDPM's training calls (setting either moves dsg_generation: a captured step is captured again)
         self.train_law = None             # (handle, the timesteps.TrainLaw), or None: dsg_set_train_law
         self.train_report = None          # (handle, sq tensor, rows tensor), or None: dsg_set_train_report

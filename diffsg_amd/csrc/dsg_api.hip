@@ -18,6 +18,7 @@
 #include "dsg_mlp.hpp"
 #include "dsg_ppo.hpp"
 #include "dsg_gd.hpp"
+#include "dsg_multistep.hpp"
 #include "dsg_own.hpp"
 #include "../../include/diffsg.h"
 
@@ -201,6 +202,36 @@ int dsg_set_step_guidance(dsg_handle* h, const float* g_host, int n) {
     HIPCK(hipMemcpy(h->guid_dev, g_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     h->guid_host.assign(g_host, g_host + n);
     h->guid_n = n;
+    return 0;
+}
+
+int dsg_set_step_history(dsg_handle* h, const float* hist_host, int n) {
+    if (!h) return fail("null handle");
+    if (n < 0) return fail("dsg_set_step_history: n = %d is negative", n);
+    if (!hist_host || n == 0) { h->hist_n = 0; return 0; }     // nothing is overwritten: an enqueued call keeps reading the buffer
+    for (int j = 0; j < 3 * n; ++j)
+        if (!(fabsf(hist_host[j]) <= 3.402823466e38f))            // NaN and the infinities fail the comparison
+            return fail("dsg_set_step_history: row %d holds %g: the rows {m, p, q} are finite", j / 3, (double)hist_host[j]);
+    auto stores = [&](int j) { return hist_host[3 * j + 1] != 0.f || hist_host[3 * j + 2] != 0.f; };
+    if (hist_host[3 * (n - 1)] != 0.f)
+        return fail("dsg_set_step_history: row %d, the first step of a call, has m = %g: there is no history to read yet", n - 1,
+                    (double)hist_host[3 * (n - 1)]);
+    for (int j = 0; j + 1 < n; ++j)
+        if (hist_host[3 * j] != 0.f && !stores(j + 1))
+            return fail("dsg_set_step_history: row %d reads the history (m = %g) but row %d, the step before it, stores none (p = q = 0)", j,
+                        (double)hist_host[3 * j], j + 1);
+    DeviceGuard dg(h);
+    // an enqueued call may still read the old rows; the step graphs hold neither the buffer nor the values and stay
+    HIPCK(hipDeviceSynchronize());
+    if (!h->hist_call) HIPCK(h->hist_call.alloc(1));
+    if (n > h->hist_cap) {      // the new buffer first: a failed allocation leaves the table the handle holds as it was
+        DevBuf<float> grown;
+        HIPCK(grown.alloc((size_t)3 * n));
+        h->hist_dev = std::move(grown);
+        h->hist_cap = n;
+    }
+    HIPCK(hipMemcpy(h->hist_dev, hist_host, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice));
+    h->hist_n = n;
     return 0;
 }
 

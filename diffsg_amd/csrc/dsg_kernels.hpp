@@ -1264,8 +1264,13 @@ __device__ __forceinline__ StepSetting step_setting(const float* row, float omeg
 // SCHED (k_update_sched, k_update_var_sched; dsg_set_step_guidance): the step's weight g = guidance[step], read once in front
 // of the loop, scales omega -- omega_j = __fmul_rn(omega, g), so g = 1 gives the bits of the unscheduled form.  g == 0 is an unguided
 // step: the denoiser ran ONE pass, which wrote eps1 to plane 0 of `eps`; only that plane is read and it is taken as eps unchanged.
-template <bool VAR, bool SCHED = false>
-__device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams* __restrict__ vpp, const float* const* __restrict__ gpp = nullptr) {
+// HIST (dsg_multistep.hpp: k_update_hist, k_update_hist_sched; dsg_set_step_history): the step's row {m, p, q} of the history
+// table, read once in front of the loop.  out = v + m * hist (hist READ only where m != 0) and hist <- p * y_old + q * eps (STORED only where
+// p != 0 || q != 0), both uniform per launch: a step with m = p = q = 0 moves the bytes of the form without a history.  Never with VAR.
+template <bool VAR, bool SCHED = false, bool HIST = false>
+__device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams* __restrict__ vpp, const float* const* __restrict__ gpp = nullptr,
+                                            float* __restrict__ hist = nullptr, const float* const* __restrict__ hpp = nullptr) {
+    static_assert(!(VAR && HIST), "chunk variants and a step history exclude each other");
     const int step = *a.step_ptr;
     const CallParams cp = *a.cp;
     VarParams vp{};
@@ -1275,15 +1280,19 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
     const bool one_pass = SCHED && g == 0.f;
     if constexpr (VAR) vp = *vpp;
     else st = step_setting(cp.coef + 4 * step, SCHED ? __fmul_rn(cp.omega, g) : cp.omega);
+    float hm = 0.f, hp = 0.f, hq = 0.f;
+    if constexpr (HIST) { const float* hrow = *hpp + 3 * (size_t)step; hm = hrow[0]; hp = hrow[1]; hq = hrow[2]; }
+    const bool h_read = HIST && hm != 0.f, h_store = HIST && (hp != 0.f || hq != 0.f);
     const size_t n4 = (a.n + 3) / 4;
     // plain: null on a noise-free step.  VAR: the row base, dereferenced by noisy chunks only (rows exist for step >= 2)
     const float* zbase = (cp.z && (VAR || st.noisy)) ? cp.z + (size_t)(cp.T - 1 - step) * a.n : nullptr;
     float* rec = (!VAR && cp.rec_eps) ? cp.rec_eps + (size_t)(cp.T - 1 - step) * a.n : nullptr;
     float* recy = (!VAR && a.record_y && cp.rec_y) ? cp.rec_y + (size_t)(cp.T - 1 - step) * a.n : nullptr;
     // whole quads, 16-byte aligned everywhere: one dwordx4 per stream and thread (same arithmetic per element)
-    const bool quads = (a.n & 3) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zbase) |
-                         reinterpret_cast<uintptr_t>(rec) | reinterpret_cast<uintptr_t>(recy)) & 15) == 0;
+    bool quads = (a.n & 3) == 0 &&
+                 ((reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(zbase) |
+                   reinterpret_cast<uintptr_t>(rec) | reinterpret_cast<uintptr_t>(recy)) & 15) == 0;
+    if constexpr (HIST) quads = quads && (reinterpret_cast<uintptr_t>(hist) & 15) == 0;
     for (size_t i4 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i4 < n4; i4 += (size_t)gridDim.x * blockDim.x) {
         if constexpr (VAR) {
             const size_t c = cp.chunk_n4 ? i4 / cp.chunk_n4 : 0;
@@ -1305,6 +1314,20 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
                 const float v = __fmul_rn(__fsub_rn(ya[p], __fmul_rn(c1, ea[p])), c2);
                 out[p] = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
             }
+            if constexpr (HIST) {
+                if (h_read) {
+                    const float4 hv = ld4(hist + i4 * 4);
+                    const float ha[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) out[p] = __fadd_rn(out[p], __fmul_rn(hm, ha[p]));
+                }
+                if (h_store) {
+                    float hn[4];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) hn[p] = __fadd_rn(__fmul_rn(hp, ya[p]), __fmul_rn(hq, ea[p]));
+                    st4(hist + i4 * 4, make_float4(hn[0], hn[1], hn[2], hn[3]));
+                }
+            }
             if (rec) st4(rec + i4 * 4, make_float4(ea[0], ea[1], ea[2], ea[3]));
             st4(a.y + i4 * 4, make_float4(out[0], out[1], out[2], out[3]));
             if (recy) st4(recy + i4 * 4, make_float4(out[0], out[1], out[2], out[3]));
@@ -1317,8 +1340,13 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a, const VarParams
                 if (zrow) zz[p] = zrow[i];
                 const float e = one_pass ? a.eps[i] : __fsub_rn(__fmul_rn(w1, a.eps[a.n + i]), __fmul_rn(omega, a.eps[i]));
                 if (rec) rec[i] = e;
-                const float v = __fmul_rn(__fsub_rn(a.y[i], __fmul_rn(c1, e)), c2);
-                const float o = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
+                const float yo = a.y[i];
+                const float v = __fmul_rn(__fsub_rn(yo, __fmul_rn(c1, e)), c2);
+                float o = noisy ? __fadd_rn(v, __fmul_rn(c3, zz[p])) : v;
+                if constexpr (HIST) {
+                    if (h_read) o = __fadd_rn(o, __fmul_rn(hm, hist[i]));
+                    if (h_store) hist[i] = __fadd_rn(__fmul_rn(hp, yo), __fmul_rn(hq, e));
+                }
                 a.y[i] = o;
                 if (recy) recy[i] = o;
             }

@@ -113,8 +113,9 @@ constexpr int kWgForkMinTiles = 1024;
 // (runs of 1, 2, 4, 8, 16, 32), and the shape they were captured for
 constexpr int kStepRunGraphs = 6;
 // the kinds of a step: the plain one, and under a guidance schedule (dsg_set_step_guidance) the two-pass step with the
-// scheduled update and the one-pass (unguided) step
-enum StepKind { STEP_PLAIN = 0, STEP_SCHED = 1, STEP_ONEPASS = 2, kStepKinds = 3 };
+// scheduled update and the one-pass (unguided) step; and the same three with the history form of the update (dsg_set_step_history,
+// k_update_hist, k_update_hist_sched), STEP_HIST + the kind without a history
+enum StepKind { STEP_PLAIN = 0, STEP_SCHED = 1, STEP_ONEPASS = 2, STEP_HIST = 3, STEP_HIST_SCHED = 4, STEP_HIST_ONEPASS = 5, kStepKinds = 6 };
 struct StepGraphs {
     GraphExec exec[kStepKinds][1 + kStepRunGraphs];
     int rows = -1, chunks = -1, chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
@@ -202,6 +203,7 @@ struct dsg_handle {
         DevBuf<int> ts_ident;       // [rows] identity index
         DevBuf<float> eps;          // [2][rows][D]
         DevBuf<float> ywork;        // [rows][D]
+        DevBuf<float> hist;         // [rows][D]: the history term of a two-step plan (dsg_set_step_history); allocated by the first call under one
     } fw;
     size_t ce_per_tile = 0;
     size_t zero_off = 0;        // 128 zero floats in the arena
@@ -217,6 +219,11 @@ struct dsg_handle {
     DevBuf<float> guid_dev; int guid_n = 0, guid_cap = 0;
     std::vector<float> guid_host;
     DevBuf<const float*> guid_call;
+    // dsg_set_step_history: one row {m, p, q} per step index of a sampling call; hist_n == 0: none held.  The buffer only
+    // grows and is kept when the setting is removed.  The step graphs of the history kinds hold `hist_call` (one pointer, allocated once)
+    // and the workspace tensor fw.hist, never this buffer: k_set_guidance writes its address into `hist_call` per call.
+    DevBuf<float> hist_dev; int hist_n = 0, hist_cap = 0;
+    DevBuf<const float*> hist_call;
     double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device, not owned), reduced across ranks by `renorm_fn`
     void (*renorm_fn)(void*) = nullptr; void* renorm_user = nullptr;
     int device = 0;              // the device that was current in dsg_create: the settings / status entry points select it themselves

@@ -7,8 +7,9 @@ namespace {
 // The form of a call's steps, built once by sample_impl: one call or `chunks` independent ones of `chunk_n` elements (0: one call), with
 // per-chunk settings (`var`, chunk variants) or without, and the renorm partial sums -- one call: the handle's two partial rows; chunked:
 // [chunks][kRedBlocks] twice, one grid row per chunk.  `sched`: the handle holds a guidance schedule (dsg_set_step_guidance): the update
-// is the scheduled form, and a step is two-pass or one-pass (StepKind).
-struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; bool sched; };
+// is the scheduled form, and a step is two-pass or one-pass (StepKind).  `hist`: the handle holds a step history (dsg_set_step_history):
+// the update is the history form (dsg_multistep.hpp), never together with `var`.
+struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; bool sched; bool hist; };
 
 // The two contexts of a call: ctx[0] two passes (unconditional tiles first), ctx[1] the one pass of an unguided step, with the resident
 // table set of each (dsg_handle::tabs).  Only a call whose schedule has a zero builds and prepares ctx[1].
@@ -36,7 +37,9 @@ int enqueue_step(dsg_handle* h, const StepCtxs& cs, bool one_pass, const UpdateA
     UpdateArgs ua = u;
     ua.record_y = renorm ? 0 : 1;
     const float* const* gpp = h->guid_call;
-    if (f.var && f.sched) hipLaunchKernelGGL(k_update_var_sched, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, gpp);
+    if (f.hist && f.sched) hipLaunchKernelGGL(k_update_hist_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp, h->fw.hist.get(), (const float* const*)h->hist_call);
+    else if (f.hist) hipLaunchKernelGGL(k_update_hist, dim3(ublocks), dim3(256), 0, s, ua, h->fw.hist.get(), (const float* const*)h->hist_call);
+    else if (f.var && f.sched) hipLaunchKernelGGL(k_update_var_sched, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, gpp);
     else if (f.var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
     else if (f.sched) hipLaunchKernelGGL(k_update_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp);
     else hipLaunchKernelGGL(k_update, dim3(ublocks), dim3(256), 0, s, ua);
@@ -80,7 +83,9 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     if (h->grid_n && T != h->grid_n) return fail("dsg_sample: the handle's step grid (dsg_set_step_grid) has %d steps, the call has T = %d", h->grid_n, T);
     if (h->guid_n && T != h->guid_n)
         return fail("dsg_sample: the handle's guidance schedule (dsg_set_step_guidance) has %d weights, the call has T = %d", h->guid_n, T);
-    const bool sched = h->guid_n > 0;
+    if (h->hist_n && T != h->hist_n)
+        return fail("dsg_sample: the handle's step history (dsg_set_step_history) has %d rows, the call has T = %d", h->hist_n, T);
+    const bool sched = h->guid_n > 0, hist = h->hist_n > 0;
     // step k of the call (step index T-1-k) is unguided: one denoiser pass
     auto unguided = [&](int k) { return sched && h->guid_host[(size_t)(T - 1 - k)] == 0.f; };
     bool any_one_pass = false;
@@ -93,6 +98,9 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     const bool var = h->var_chunks > 0;
     const int n_default = h->grid_n ? h->grid_renorm : (T < 4 ? T : 4);  // steps i > T-5 (MSR.py:136), or dsg_set_step_grid's count
     int n_renorm = n_default;
+    if (var && hist)
+        return fail("dsg_sample_chunked: the handle holds chunk variants (dsg_set_chunk_variants) and a step history (dsg_set_step_history): "
+                    "the variant form of the update has no history, remove one of them");
     if (var) {
         if (chunk_rows <= 0)
             return fail("dsg_sample: the handle holds chunk variants (dsg_set_chunk_variants) for %d chunk(s): call dsg_sample_chunked, or remove them", h->var_chunks);
@@ -109,6 +117,9 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         }
     }
     if (ensure_workspace(h, B, T)) return 1;
+    // the history tensor: sized like ywork, on the first call under a history of this workspace (no graph of a history kind exists yet:
+    // free_workspace drops tensor and graphs together)
+    if (hist && !h->fw.hist) HIPCK(h->fw.hist.alloc((size_t)h->cap_rows * h->d.input_dim));
     const int D = h->d.input_dim, CG = groups_of(h->d.cond_dim), tpp = cdiv(B, 32);
     const size_t n = (size_t)B * D;
     const size_t chunk_n = chunks > 1 ? (size_t)chunk_rows * D : 0;
@@ -150,6 +161,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         hipLaunchKernelGGL(k_set_var, dim3(1), dim3(64), 0, s, h->var_call.get(), vp);
     }
     if (sched) hipLaunchKernelGGL(k_set_guidance, dim3(1), dim3(64), 0, s, h->guid_call.get(), (const float*)h->guid_dev);
+    if (hist) hipLaunchKernelGGL(k_set_guidance, dim3(1), dim3(64), 0, s, h->hist_call.get(), (const float*)h->hist_dev);   // (the same one-word store)
 
     StepCtxs cs{{RunCtx{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true},
                  RunCtx{B, 1, 0, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true}}};
@@ -166,7 +178,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     }
     if (prepare_fused(h, cs.ctx[0], s)) return 1;
     const StepForm form{chunks, chunk_n, var, chunks > 1 ? h->red_chunks : h->red,
-                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks, sched};
+                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks, sched, hist};
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
@@ -196,7 +208,8 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         // call is cut into runs of equal kind; none of the graphs depends on the weights, only the host's choice among them does.
         // captured lazily: only the run lengths a call replays (a one-off batch size pays for its own decomposition, not for
         // 64 steps of nodes)
-        auto kind_of = [&](int k) { return !sched ? STEP_PLAIN : unguided(k) ? STEP_ONEPASS : STEP_SCHED; };
+        // under a step history the same three with the history form of the update (STEP_HIST ...): the rows {m, p, q} are read on the device
+        auto kind_of = [&](int k) { return (hist ? (int)STEP_HIST : 0) + (!sched ? STEP_PLAIN : unguided(k) ? STEP_ONEPASS : STEP_SCHED); };
         auto graph_of = [&](int kind, int variant) -> int {
             GraphExec& ge = G.exec[kind][variant];
             if (ge) return 0;
@@ -205,7 +218,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             HIPCK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = 0;
             for (int k = 0; k < run && !rc; ++k)
-                rc = enqueue_step(h, cs, kind == STEP_ONEPASS, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
+                rc = enqueue_step(h, cs, kind == STEP_ONEPASS || kind == STEP_HIST_ONEPASS, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));

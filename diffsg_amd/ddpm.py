@@ -100,7 +100,8 @@ class DDPMCore(nn.Module):
           plan        a `steps.StepPlan`: run its K steps (a sub-sequence of the trained ones, or the last k + 1) instead of all T;
                       `noise` is then (K-2, B, D) and the recorded trajectory (B, K*D).  None: all T trained steps.  A plan with
                       `guidance` (steps.with_guidance) guides step j with omega * g_j and runs the conditional denoiser pass alone
-                      where g_j == 0 (the recorded eps of such a step is that pass's output); DESIGN.md 16.
+                      where g_j == 0 (the recorded eps of such a step is that pass's output); DESIGN.md 16.  A plan with `history`
+                      (steps.dpmpp_2m, steps.with_history) runs the update with the history term; DESIGN.md 18.
         """
         K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
@@ -176,6 +177,12 @@ class DDPMCore(nn.Module):
             from .steps import check_guidance
             try:
                 check_guidance(plan.guidance, K)
+            except ValueError as e:
+                raise ValueError(f"step plan: {e}") from None
+        if plan.history is not None:
+            from .steps import check_history
+            try:
+                check_history(plan.history, K)
             except ValueError as e:
                 raise ValueError(f"step plan: {e}") from None
         self._check_noise(noise, K, cond.shape[0], f" for a plan of {K} steps")
@@ -263,6 +270,28 @@ class DDPMCore(nn.Module):
                 _lib.check(_lib.lib().dsg_set_step_guidance(hd, arr, len(key)))
         nat.step_guidance = (hd, key, g, g._version)
 
+    def _use_history(self, hd, hist, dev):
+        """Make handle `hd` hold the history table `hist` (None: none), as `_use_guidance` holds the weights: repeated calls with the same
+        rows set nothing (setting them synchronises the device), a plan without a history after one with it removes them."""
+        import ctypes
+        nat = self.model._native
+        held = nat.step_history                          # (handle, the rows, their tensor and its version)
+        if held is not None and held[0] != hd:
+            held = None
+        if hist is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_step_history(hd, None, 0))
+                nat.step_history = None
+            return
+        if held is not None and held[2] is hist and held[3] == hist._version:      # the same tensor, unchanged: nothing to convert or compare
+            return
+        key = tuple(hist.detach().cpu().to(torch.float32).reshape(-1).tolist())
+        if held is None or held[1] != key:
+            arr = (ctypes.c_float * len(key))(*key)
+            with torch.cuda.device(dev):          # a refused or failed call leaves what the handle holds, and this record of it, unchanged
+                _lib.check(_lib.lib().dsg_set_step_history(hd, arr, len(key) // 3))
+        nat.step_history = (hd, key, hist, hist._version)
+
     def _resolve_variants(self, variants, cond, noise):
         """[(omega, plan)] of a list of variants with `None` plans replaced by the identity plan (all T trained steps, the trained table's
         own rows, min(T, 4) renorm steps), and the step count K they share -- after the checks that need no device: every plan passes
@@ -285,6 +314,9 @@ class DDPMCore(nn.Module):
                 self._plan_steps(plan, cond, noise)
             except ValueError as e:
                 raise ValueError(f"variant {k}: {e}") from None
+            if plan.history is not None:
+                raise ValueError(f"variant {k}: the plan has a history table (steps.dpmpp_2m, steps.with_history): chunk variants have no "
+                                 "history form of the update, give it as `plan=` instead")
             first = out[0][1] if out else plan
             if not ((plan.taus is first.taus or tuple(plan.taus) == tuple(first.taus)) and (plan.t is first.t or torch.equal(plan.t.cpu(), first.t.cpu()))):
                 raise ValueError(f"variant {k} has another step grid (taus / t) than variant 0: the variants of one call share the time "
@@ -317,6 +349,7 @@ class DDPMCore(nn.Module):
             if not (grid is not None and grid[0] == hd and torch.equal(grid[1].t, plan0.t)):   # the renorm count of the grid is not read
                 self._use_plan(hd, plan0, dev)
         self._use_guidance(hd, plan0.guidance, dev)           # the schedule the variants share
+        self._use_history(hd, None, dev)                      # variants have none (_resolve_variants)
         # the distinct coefficient tensors, stacked once
         coefs, table = [], []
         for _, p in chunks:
@@ -356,6 +389,7 @@ class DDPMCore(nn.Module):
         self._use_variants(hd, None, dev)  # a sample() call is no chunked call: per-chunk settings of an earlier one go
         coef = self._use_plan(hd, plan, dev)
         self._use_guidance(hd, None if plan is None else plan.guidance, dev)
+        self._use_history(hd, None if plan is None else plan.history, dev)
         flags = 2 if profile else (0 if use_graph else 1)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().dsg_sample_rec(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, seed, float(omega), _lib.ptr(coef), T,
@@ -427,6 +461,7 @@ class DDPMCore(nn.Module):
                 self._use_variants(hd, None, dev)
                 coef = self._use_plan(hd, plan, dev)
                 self._use_guidance(hd, None if plan is None else plan.guidance, dev)
+                self._use_history(hd, None if plan is None else plan.history, dev)
             else:
                 coef = self._use_variants(hd, variants, dev)      # [tables][K][4]; `omega` is not read by the call
             with torch.cuda.device(dev):

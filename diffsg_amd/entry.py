@@ -4,8 +4,9 @@ own: the data loader, `build_model`, unscaling, the decoder and the objective, t
 
 The sampler options of `load_test_msr`, `load_test_co` and `load_test_nu`, beyond the reference's arguments:
   repeats   > 1: that many draws per test row, the one with the best objective scored (DDPM.sample_best); 1 is the reference's single draw.
-  steps     = K: sample on K of the T trained steps (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`); None: all T, as
-            the reference.
+  steps     = K: sample on K of the T trained steps (`steps.strided`, or `steps.ddim` with `sampler="ddim"` and `eta`, or
+            `steps.dpmpp_2m` with `sampler="dpmpp2m"`: the two-step rule of DESIGN.md 18); None: all T, as the reference.  A variant's
+            plan must not carry a history table (a `dpmpp_2m` plan): the per-chunk form of the update has none.
   variants  a list of (omega, plan) sampler settings cycled over the `repeats` rounds (round r runs variants[r % len(variants)],
             DDPM.sample_best); `omega` and `steps` / `sampler` / `eta` stay the single-setting spelling and are not read then.
             A plan of a variant may carry a guidance schedule (`steps.with_guidance(plan_or_model, g)`, DESIGN.md 16: step j guided with

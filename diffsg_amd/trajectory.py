@@ -26,7 +26,7 @@ def _load(diffusion_model, ckpt_path, device):
 def record_trajectories(diffusion_model, X_test, omega, batch_size=None, steps=None, sampler="strided", eta=0.0):
     """(rows, T*D) float array of decoded trajectories.  batch_size=None: one `sample()` call over all rows (the MSR / NU
     scripts); an int: chunks of that many rows written into place (co_trajectory_gen.py:48-56).  `steps` = K: the K-step
-    trajectory of `steps.strided` (`sampler="ddim"`: `steps.ddim` with `eta`), (rows, K*D); None: all T trained steps."""
+    trajectory of `steps.strided` (`sampler="ddim"`: `steps.ddim` with `eta`; `sampler="dpmpp2m"`: `steps.dpmpp_2m`), (rows, K*D); None: all T trained steps."""
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
     K = diffusion_model.T if plan is None else plan.K

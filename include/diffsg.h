@@ -236,6 +236,27 @@ int dsg_set_step_grid(dsg_handle* h, const float* t_host, int n, int renorm_step
  * graphs depend neither on the values nor on the buffer: setting, changing or removing the schedule drops none. */
 int dsg_set_step_guidance(dsg_handle* h, const float* g_host, int n);
 
+/* Step history: the second per-step row of a two-step (linear multistep) solver plan, DPM-Solver++(2M) for one.
+ * `hist_host` is a HOST array of n rows {m, p, q} of finite floats, indexed like `coef` (index n-1 runs first).  While it is held, the
+ * handle keeps a float32 tensor `hist` with one value per element of y, and step j of dsg_sample / dsg_sample_rec / dsg_sample_chunked,
+ * with v the result of the update without a history (the noise term included) and eps the guided eps of the step (eps1 on an unguided
+ * step of a guidance schedule), computes in round-to-nearest float32 operations, no contraction
+ *     out      = m != 0 ? v + m * hist : v               hist is READ only where m != 0
+ *     hist_new = p * y_old + q * eps                      STORED only where p != 0 || q != 0; y_old: y before this step
+ *     y <- out
+ * The early renorm and the trajectory record act on `out`; rec_eps carries eps.  A step with m = p = q = 0 reads and writes what the
+ * step without a history does.  hist_host == NULL or n == 0 removes the setting.  Refused: n < 0; a non-finite value; m != 0 in row
+ * n-1 (the first step of a call has no history); m != 0 in row j while row j+1 stores nothing (p = q = 0: the step would read another
+ * call's data).  With the setting held the three sampling entry points fail before anything is enqueued when T != n, and a chunked call
+ * on a handle that also holds chunk variants (dsg_set_chunk_variants) is refused: the variant form of the update has no history.
+ * dsg_unet_forward, dsg_time_op and the training steps ignore the setting.
+ * The rows are copied into a device buffer the handle owns.  Like the other settings calls this one takes no stream: it selects the
+ * handle's device itself and synchronises that device before it overwrites the buffer (an enqueued call may still read it); removing
+ * the setting overwrites nothing and does not synchronise.  The `hist` tensor belongs to the forward workspace (allocated by the first
+ * call under a history, sized like the work copy of y).  The captured step graphs depend neither on the values nor on the buffer:
+ * setting, changing or removing the history drops none. */
+int dsg_set_step_history(dsg_handle* h, const float* hist_host, int n);
+
 /* Chunk variants: a per-chunk sampler setting for dsg_sample_chunked.  Every chunk of a chunked call is an independent sample() call; with
  * this per-handle setting the calls may also differ in omega, in the coefficient table and in the number of early renormalised steps:
  *   omega_host   HOST array [chunks]: chunk c is guided with omega_host[c];
