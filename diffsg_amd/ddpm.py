@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import _lib
 from .ema import ExponentialMovingAverage
+from .parallel import fold_rank
 
 _BUFFERS = ("betas", "alphas", "alphas_cumprod", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
             "reciprocal_sqrt_alphas", "remove_noise_coeff", "sqrt_betas")
@@ -825,7 +826,7 @@ class DDPMCore(nn.Module):
         self._draw_calls += 1
         # data parallel: every rank must draw DIFFERENT ts / noise / mask for its rows (dp_context only de-correlates torch's
         # generator): the rank is folded into the Philox key, rank 0 keeps the plain seed
-        seed = (int(self.device_draws) ^ (_dp_rank() * 0x9E3779B97F4A7C15)) & (2 ** 64 - 1)
+        seed = fold_rank(self.device_draws, _dp_rank())
         sa, sb = _lib.ptr(self.sqrt_alphas_cumprod), _lib.ptr(self.sqrt_one_minus_alphas_cumprod)
 
         if self._splits(B):

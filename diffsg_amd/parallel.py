@@ -82,13 +82,33 @@ class global_renorm:
         return False
 
 
+RANK_FOLD = 0x9E3779B97F4A7C15
+
+
+def fold_rank(seed, rank):
+    """The Philox seed of rank `rank` under the job's seed: seed ^ rank * RANK_FOLD (64 bits).  Rank 0 keeps the plain seed; the
+    ranks of a job draw from different keys.  One rule for the training draws (`DDPM.device_draws`) and for `sample_sharded`."""
+    return (int(seed) ^ (int(rank) * RANK_FOLD)) & (2 ** 64 - 1)
+
+
 def sample_sharded(ddpm, cond_all, omega=1.0, gather=False, global_renorm_stats=False, **kw):
     """Each rank samples its shard of `cond_all`.  Default: NO collective -- every shard is its own `sample()` call, exactly
     as the reference treats its 512-row chunks (the early-step renorm is per call).  global_renorm_stats=True: the renorm uses
     the whole batch's statistics (`global_renorm`; 3 scalars all-reduced on 4 steps), matching one reference call on
-    `cond_all`.  With gather=True the shards are all-gathered afterwards (a convenience for evaluation, outside the path)."""
+    `cond_all`.  With gather=True the shards are all-gathered afterwards (a convenience for evaluation, outside the path).
+
+    The seed of the device draws: `seed=` if given, otherwise one draw from torch's global generator (the draw `sample()` would make
+    itself) -- taken ONCE, then the rank is folded in: rank r calls `sample(seed=fold_rank(seed, r))`, rank 0 with the seed as it is.
+    Without the fold every rank would hand `sample()` the same seed (the given one, or one from generators that the ranks of a job
+    typically seed alike), and row i of every shard would get the same y_T and the same noise.  `host_rng=True` calls draw with
+    torch.randn as the reference does and are passed on unchanged."""
     rank, ws = world()
     lo, hi = shard_rows(cond_all.shape[0], rank, ws)
+    if not kw.get("host_rng"):
+        seed = kw.get("seed")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        kw["seed"] = fold_rank(seed, rank)
     err, y = None, None
     if global_renorm_stats and ws > 1:
         with global_renorm(ddpm) as gr:

@@ -57,6 +57,41 @@ def _worker(rank, ws, port, q):
         lo, hi = par.shard_rows(11, rank, ws)
         assert par.sample_sharded(Fake(), cond_all, 0.5).shape[0] == hi - lo
 
+        # ---- the seed of a sharded call: taken once, then the rank folded in as the training draws fold it -- row i of every shard
+        # must not get rank 0's y_T and noise.  A stand-in that records what it is given.
+        class Recording:
+            def sample(self, cond, omega=1.0, **kw):
+                self.kw = kw
+                return cond * 2.0
+
+        def seeds_of_all_ranks(**kw):
+            rec = Recording()
+            par.sample_sharded(rec, cond_all, 0.5, **kw)
+            mine = torch.tensor([rec.kw["seed"] >> 32, rec.kw["seed"] & 0xFFFFFFFF], dtype=torch.int64)
+            parts = [torch.zeros_like(mine) for _ in range(ws)]
+            dist.all_gather(parts, mine)
+            return [(int(p[0]) << 32) | int(p[1]) for p in parts], rec.kw
+        FOLD = 0x9E3779B97F4A7C15
+        for s in (1234, 2 ** 40 + 5, 2 ** 62 - 1):
+            seeds, kw_seen = seeds_of_all_ranks(seed=s, use_graph=False)
+            assert seeds[0] == s and len(set(seeds)) == ws, (s, seeds)
+            assert seeds == [(s ^ (r * FOLD)) & (2 ** 64 - 1) for r in range(ws)] == [par.fold_rank(s, r) for r in range(ws)]
+            assert kw_seen["use_graph"] is False                 # the other keywords pass through
+        torch.manual_seed(77)                                    # no seed given, generators seeded alike on every rank
+        want = int(torch.randint(0, 2 ** 62, (1,)).item())
+        torch.manual_seed(77)
+        seeds, _ = seeds_of_all_ranks()
+        assert seeds[0] == want and seeds == [par.fold_rank(want, r) for r in range(ws)] and len(set(seeds)) == ws, seeds
+        after = int(torch.randint(0, 2 ** 62, (1,)).item())
+        torch.manual_seed(77)
+        torch.randint(0, 2 ** 62, (1,))
+        assert after == int(torch.randint(0, 2 ** 62, (1,)).item())          # exactly one draw was taken
+        rec = Recording()
+        par.sample_sharded(rec, cond_all, 0.5, host_rng=True)    # torch.randn draws, as the reference: passed on unchanged
+        assert rec.kw == {"host_rng": True}
+        # the same fold keys the training draws: rank 0 the plain seed
+        assert par.fold_rank(4242, 0) == 4242 and par.fold_rank(4242, 1) == 4242 ^ FOLD
+
         # ---- training: ONE all-reduce over the flat bucket gives the mean of the ranks' gradients in every .grad view
         total = sum(p.numel() for p in d.model.parameters())
         d._grad_pool = []

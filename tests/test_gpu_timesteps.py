@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import philox_ref as P
 import timesteps_ref as R
 from _util import GOLD
 from oracle import ddpm_oracle as O
@@ -81,11 +82,14 @@ def test_the_laws_draw_is_the_stated_integer_rule(name, kind, B):
     d.train_law = lw
     d.loss_report(True)
     for call in range(2):
-        u24 = _device_draws(seed, call, G24, keep, B, D)[0].cpu().numpy()          # T = 2^24: ts == u24 exactly
+        # the 24-bit word of every row from the CPU restatement of the draws (tests/philox_ref.py), not from the library: T = 2^24 gives
+        # ts == u24 exactly, and the device's own call with that T must agree
+        u24 = P.train_draws(seed, call, G24, keep, B, D)[0].astype(np.int64)
         assert u24.min() >= 0 and u24.max() < G24
+        assert np.array_equal(_device_draws(seed, call, G24, keep, B, D)[0].cpu().numpy(), u24)
         _, noise, mask = _device_draws(seed, call, T, keep, B, D)
         if lw.cdf24 is None:
-            ts_want = _device_draws(seed, call, T, keep, B, D)[0].cpu().numpy().astype(np.int64)   # the uniform draw, as without a law
+            ts_want = P.train_draws(seed, call, T, keep, B, D)[0].astype(np.int64)                 # the uniform draw, as without a law
         else:
             ts_want = R.expected_ts(lw.cdf24, u24)
         d.device_draws, d._draw_calls = seed, call
