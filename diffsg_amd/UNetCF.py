@@ -334,7 +334,9 @@ class UNet1D(nn.Module):
 
     def range_status(self):
         """The bits of `dsg_range_status_stream` over every handle of the module: 1 -- since the last query a raw operand or the condition
-        left fp16's range (cleared by the query); 2 -- the bound WEIGHTS are outside the split path's envelope (a LayerNorm with
+        left fp16's range -- above 6e4, or a whole row whose bound is under 2^-9 (a row of the network input: whose largest entry is under
+        2^-14), where the lo halves are subnormals; a small half of a shortcut's row beside a half of order 1 is NOT reported, the bound
+        is the concatenated row's ("what stays open") -- (cleared by the query); 2 -- the bound WEIGHTS are outside the split path's envelope (a LayerNorm with
         16 * (max|gamma| * sqrt(features) + max|beta|) > 6e4, or a Linear with max|W| >= 2^21): not cleared, the next
         bind recomputes it.  Either way the split-f16 results are not to be trusted."""
         bits = 0
@@ -367,7 +369,8 @@ class UNet1D(nn.Module):
                                "16 * (max|gamma| * sqrt(features) + max|beta|) > 6e4, or a Linear with max|W| >= 2^21); "
                                "its results are invalid for these weights -- use set_precision('f32') for this model")
         if bits:
-            raise RuntimeError("libdiffsg_hip: an activation exceeded the fp16 range of the split-f16 path (|x| > 6e4); "
+            raise RuntimeError("libdiffsg_hip: an activation left the fp16 range of the split-f16 path (|x| > 6e4, or a whole row too small for it: "
+                               "bound under 2^-9, a row of the network input under 2^-14); "
                                "the results of the last calls are invalid -- use set_precision('f32') for this model")
 
     def set_launch_policy(self, coop_max_tiles=-1, narrow_small_max_tiles=-1):

@@ -58,6 +58,11 @@ __device__ __forceinline__ unsigned xhalf_swap_lo(unsigned v, unsigned& hi) {
     hi = r[1];
     return r[0];
 }
+__device__ __forceinline__ float xhalf_max(float v) {
+    unsigned hi;
+    const unsigned lo = xhalf_swap_lo(__float_as_uint(v), hi);
+    return fmaxf(__uint_as_float(lo), __uint_as_float(hi));
+}
 __device__ __forceinline__ float xhalf_sum(float v) {
     unsigned hi;
     const unsigned lo = xhalf_swap_lo(__float_as_uint(v), hi);

@@ -31,8 +31,25 @@ constexpr float kRawScale = 1.0f;        // B operands that are raw residual-str
 // bounds its rows -- |mean| + sqrt(M2) >= max|x| from the LayerNorm statistics it has anyway -- and raises the handle's range
 // flag above this limit; dsg_range_status reports it (the caller then switches to DSG_PRECISION_F32_MFMA).
 constexpr float kRawLimit = 6.0e4f / kRawScale;
+// The low side: below 2^-4 the remainder x - hi is under 2^-14 and lo is an fp16 SUBNORMAL (spacing 2^-24): the operand carries an absolute
+// error of up to 2^-25 whatever its size, so a row whose entries are ALL small loses a bit per binade (a Linear over rows of rms 2^-10 is
+// 1.7e-5 off, of rms 2^-14 2.8e-4: DESIGN.md 7 has the curve).  A row whose bound is under kRawFloor = 2^-9 raises the same flag.  The bound
+// is about sqrt(N) times the row's rms (the error goes with the rms), so the floor sits at rms 2^-10.5 for an 8-wide row and 2^-12.5 for a
+// 128-wide one: lower than the accuracy contract alone would put it, because the shipped NU checkpoint runs rows with a bound of 0.023
+// (tests/test_envelope_cpu.py keeps a factor 8 between every shipped workload and the floor).  A bound of exactly 0 raises nothing: an
+// all-zero row (a zeroed net, the unused rows of a ragged tile) splits into exact zeros.
+constexpr float kRawFloor = 1.953125e-3f / kRawScale;
+// feature_proj bounds its rows by max|y| itself.  Its own product does not lose the bits (linear_body_h rescales a small row of y by a
+// power of two), but the weight-gradient unit of feature_proj reads y as its A operand unscaled, so a floor stays.  The shipped training
+// feeds small rows: at t = 0 an all-zero label row is x_t = sqrt(1 - acp_0) * noise = 6.4e-3 * noise, and the largest of THREE such
+// entries (MSR-3c, CO-3n) has no lower bound in distribution.  2^-14 puts the chance of such a row under the floor at
+// (0.8 * 2^-14 / 6.4e-3)^3 = 4e-7: this floor catches data in the wrong units, no more.
+constexpr float kRawFloorIn = 6.103515625e-5f / kRawScale;
 __device__ __forceinline__ void range_check(int* flag, float mean, float m2) {
-    if (flag && fabsf(mean) + sqrtf(m2) > kRawLimit) *flag = 1;
+    if (flag) {
+        const float b = fabsf(mean) + sqrtf(m2);
+        if (b > kRawLimit || (b > 0.f && b < kRawFloor)) *flag = 1;
+    }
 }
 // The other operands of the split products, and what bounds them ("the envelope"):
 //   * the condition: kActScale * silu(cond * mask) is split with no LayerNorm in front -- k_cond_frag raises the same flag above
@@ -1283,6 +1300,21 @@ __device__ __forceinline__ void linear_body_h(const LinArgsH& ah, const int tile
         range_check(a.range_flag, s.x, s.y);
     }
     float vmax = 0.f;
+    // feature_proj rescales a SMALL row of y (max|y| under 2^-3, where the split starts to lose bits) by the power of two that brings
+    // its largest entry into [0.5, 1), and un-scales the accumulator of that row: exact scalings, so such a row keeps its 22 bits at
+    // any size (3- and 5-wide rows of y at 2^-8 were 2e-5 off: nothing averages there).  Rows from 2^-3 up get the factor 1: same bits.
+    float rs = 1.f, rinv = 1.f;
+    const auto row_scale = [&]() {
+        const float rmax = xhalf_max(vmax);            // a lane holds every other quad of its row: both half-waves, one factor
+        if (rmax > 0.f && rmax < 0.125f) {
+            int e;
+            frexpf(rmax, &e);
+            e = e < -96 ? -96 : e;
+            rs = ldexpf(1.f, -e); rinv = ldexpf(1.f, e);
+        }
+        return rmax;
+    };
+    float rmax = 0.f;
     if (INMODE == IN_FRAG) {
         if constexpr (DEEP)
             chain_from_mem_h_batched<NT, LNACT, 2>(acc, a.in.data + (size_t)seg_tile(a.in, tile) * KG * 256 + lane * 4, KG, ah.Wh + lane,
@@ -1301,23 +1333,30 @@ __device__ __forceinline__ void linear_body_h(const LinArgsH& ah, const int tile
                 const int f = 8 * q + 4 * h;
                 xq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (q < 2 * KS && row < a.nrows && f < a.in_width) xq[q] = ld4(a.in_rm + (size_t)row * a.in_width + f);
+                vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(xq[q].x), fabsf(xq[q].y))), fmaxf(fabsf(xq[q].z), fabsf(xq[q].w)));
             }
+            rmax = row_scale();
 #pragma unroll
             for (int S = 0; S < kPreS; ++S) {
                 if (S < KS) {
                     HFrag<NT> wc;
                     load_hfrag<NT>(wc, ah.Wh + (size_t)S * 128 + lane, nt_stride);
                     const float4 x0 = xq[2 * S], x1 = xq[2 * S + 1];
-                    const float v[8] = {kRawScale * x0.x, kRawScale * x0.y, kRawScale * x0.z, kRawScale * x0.w,
-                                        kRawScale * x1.x, kRawScale * x1.y, kRawScale * x1.z, kRawScale * x1.w};
-#pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) vmax = fmaxf(vmax, fabsf(v[jj]));
+                    const float sc = kRawScale * rs;
+                    const float v[8] = {sc * x0.x, sc * x0.y, sc * x0.z, sc * x0.w, sc * x1.x, sc * x1.y, sc * x1.z, sc * x1.w};
                     h8 bhi, blo;
                     split8(v, bhi, blo);
                     mfma_step_h<NT>(acc, wc, bhi, blo);
                 }
             }
-        } else
+        } else {
+        for (int S = 0; S < KS; ++S)                  // the row's largest entry first (a second, cached read of a row of a few floats)
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                const int f = 8 * (2 * S + (jj >> 2)) + 4 * h + (jj & 3);
+                if (row < a.nrows && f < a.in_width) vmax = fmaxf(vmax, fabsf(a.in_rm[(size_t)row * a.in_width + f]));
+            }
+        rmax = row_scale();
         for (int S = 0; S < KS; ++S) {
             HFrag<NT> wc;
             load_hfrag<NT>(wc, ah.Wh + (size_t)S * 128 + lane, nt_stride);
@@ -1338,14 +1377,17 @@ __device__ __forceinline__ void linear_body_h(const LinArgsH& ah, const int tile
                 }
             }
 #pragma unroll
-            for (int jj = 0; jj < 8; ++jj) vmax = fmaxf(vmax, fabsf(v[jj]));
+            for (int jj = 0; jj < 8; ++jj) v[jj] *= rs;
             h8 bhi, blo;
             split8(v, bhi, blo);
             mfma_step_h<NT>(acc, wc, bhi, blo);
         }
-        if (a.range_flag && vmax > kRawLimit * kRawScale) *a.range_flag = 1;
+        }
+        // the floor is the ROW's (a 5-wide row leaves one entry to the upper half-wave).  The forward product no longer needs it; the
+        // weight-gradient unit that reads y as its A operand does
+        if (a.range_flag && (rmax > kRawLimit || (rmax > 0.f && rmax < kRawFloorIn))) *a.range_flag = 1;
     }
-    acc_unscale_add<NT>(acc, ah.kc[LNACT ? 1 : 0], a.bias, h);
+    acc_unscale_add<NT>(acc, ah.kc[LNACT ? 1 : 0] * rinv, a.bias, h);
 
     if (OUTMODE == OUT_FRAG) {
         const int NG = (a.out_width + 7) / 8;

@@ -147,7 +147,8 @@ class DDPMCore(nn.Module):
             import warnings
             why = ("the weights are outside the envelope of the split-f16 path (model.check_range() names the bound): this and every "
                    "later call runs on the exact kernels until the weights change" if bits & 2 else
-                   "activations exceeded the fp16 range of the split-f16 path")
+                   "activations left the fp16 range of the split-f16 path (above 6e4, or a whole row too small for it: bound under 2^-9, "
+                   "a row of the network input under 2^-14)")
             warnings.warn(f"DDPM.{name}: {why}; repeating the call with precision='f32'")
             out = exact()
         return out
@@ -159,7 +160,7 @@ class DDPMCore(nn.Module):
             self._range_unchecked = False
             if self.model.range_exceeded():
                 raise RuntimeError("libdiffsg_hip: an earlier sample(check_range=False) call on this model left the fp16 range of the "
-                                   "split-f16 path (|x| > 6e4): its results are invalid -- repeat it with check_range=True or "
+                                   "split-f16 path (|x| > 6e4, or a whole row under 2^-9, a row of the network input under 2^-14): its results are invalid -- repeat it with check_range=True or "
                                    "model.set_precision('f32')")
 
     def _plan_steps(self, plan, cond, noise):

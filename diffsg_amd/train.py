@@ -364,8 +364,10 @@ def step_health(diffusion_model, loss_value, device, world, where=""):
     who = "this rank" if any(here) else "another rank"
     what = []
     if bad_range:
-        what.append("an activation of the training step left the fp16 range of the split-f16 path (|x| > 6e4; the float32 reference "
-                    "has no such limit): scale the targets, or train with model.set_precision('f32')")
+        what.append("an activation of the training step left the fp16 range of the split-f16 path (|x| > 6e4, or a whole raw row too small "
+                    "for it: bound under 2^-9, a row of the network input under 2^-14; the float32 reference has no such limits): bring the "
+                    "targets to order 1 -- scale them DOWN if an activation was too large, UP if the data is in small units -- or train "
+                    "with model.set_precision('f32')")
     if bad_loss:
         what.append("the loss is not finite")
     raise FloatingPointError(f"{where}: invalid training step on {who} of {world}: " + "; ".join(what) +

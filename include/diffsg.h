@@ -86,7 +86,11 @@ int dsg_set_renorm_hook(dsg_handle* h, double* stats3, void (*reduce)(void* user
  * normalisation; LayerNorm outputs are bounded and weights are scaled at bind time).  Every kernel that splits a raw operand
  * bounds its rows by |mean| + sqrt(M2) from the LayerNorm statistics and raises a per-handle flag above 6e4 (fp16 saturates at
  * 65504: the result would be silently wrong, not inf).  The condition is such an operand too: 16 * silu(cond * mask) is split with no
- * LayerNorm in front, and the same flag comes up where it exceeds 6e4.  dsg_range_status synchronises the device, returns the flag in
+ * LayerNorm in front, and the same flag comes up where it exceeds 6e4.
+ * The envelope has a low side: below 2^-4 the lo half of a raw operand is an fp16 subnormal and the operand carries an absolute error of
+ * 2^-25, so a row whose entries are all small loses a bit per binade.  The same flag comes up for a row whose bound is above 0 and under
+ * 2^-9 (feature_proj: whose max|y| is above 0 and under 2^-14); an all-zero row raises nothing.  The condition and the weight-side
+ * conditions need no floor.  dsg_range_status synchronises the device, returns the flag in
  * *exceeded (bit DSG_RANGE_ACTIVATION) and clears it; when it is set the outputs since the last query are not to be trusted: rerun with
  * DSG_PRECISION_F32_MFMA.
  * Bit DSG_RANGE_WEIGHTS reports the bound WEIGHTS instead: dsg_bind_weights computes (on the device, no synchronise), for every LayerNorm

@@ -18,6 +18,9 @@ Everything is derived from the oracle's `unet_plan`, so the list is complete for
 that every scenario is isolated).  Amplitudes follow from the code, not from a measurement: a row with one entry A among N has
 |mean| + sqrt(M2) <= A (sqrt(1 - 1/N) + 1/N) <= 1.15 A for N >= 3, so A_IN = 5e4 stays under the limit (<= 57 500) while A_OUT = 7e4 is above
 the limit AND above fp16's largest finite value 65 504.
+
+The guard has a low side too (kRawFloor, kRawFloorIn: rows whose entries are all small); its scenarios scale whole stream segments and are
+described where they are built ("the low side", below).
 """
 import functools
 from collections import OrderedDict, namedtuple
@@ -147,8 +150,162 @@ def scenarios(name, seed, A, only=None):
     return plan, base, out
 
 
+# ------------------------------------------------------------------------------------------------ the low side
+# The guard's other edge (csrc/dsg_split.hpp: kRawFloor, kRawFloorIn): a raw operand below 2^-4 has a subnormal lo part and carries an
+# absolute error of 2^-25 (tests/split_ref.py), so a row whose entries are ALL small loses bits in proportion to its amplitude.  One outlier
+# does not make a row small: a low scenario brings a whole STREAM SEGMENT to amplitude s -- a tensor with a scalable producer
+# (feature_proj, a Down/Upsample Linear, an up block with its Linear shortcut) and the tensors identity shortcuts carry it into (out = x + h:
+# the following down blocks, the two middle blocks), up to the next block that is no identity:
+#   * the producing weight / bias pairs are multiplied by s: `feature_proj.*` or `....lin.*` or the head block's `....res.lin3.*` and
+#     `....res.shortcut.*`, and `....res.lin3.*` of every identity-carried successor (so x + h stays of size s);
+#   * the segment's columns of every raw consumer's weight are divided by s (`....shortcut.weight[:, col0:col0 + w]`, `....lin.weight`), so the
+#     products stay of order 1.  Nothing cancels: every low scenario carries an accuracy claim;
+#   * the `y` scenario multiplies the network input (the start state, the forward input, the training step's y AND noise) by s and divides
+#     `feature_proj.weight` by s.  (A sampling call renormalises y after its first steps, so only its first step reads a small y.)
+# A read is WHOLE in a scenario when every tensor of its row belongs to the segment: the kernels bound the concatenated row of a shortcut,
+# so a small half beside a half of order 1 is, by construction of that bound, not a small row (DESIGN.md 7 says what that leaves open).
+RAW_FLOOR = 2.0 ** -9      # kRawFloor: rows with 0 < |mean| + sqrt(M2) < this are reported
+RAW_FLOOR_IN = 2.0 ** -14  # kRawFloorIn: feature_proj's rows with 0 < max|y| < this are reported
+# Amplitudes, from the row bounds tests/test_envelope_cpu.py measures on the oracle's taps (float64): a whole row of a segment at amplitude s
+# has |mean| + sqrt(M2) between 1.2 s (an 8-wide row) and 26 s (a 128-wide one, about sqrt(N) times its rms), a row of y has max|y| between
+# 0.2 s and 3.9 s.  S_IN is the smallest power of two at which no such row can be within a factor 2 of its floor (1.2 * 2^-8 = 2.4 kRawFloor,
+# 0.2 * 2^-8 = 13 kRawFloorIn), S_OUT the largest at which every one must be (26 * 2^-17 = 0.1 kRawFloor, 3.9 * 2^-17 = 0.49 kRawFloorIn).
+BOUND_OVER_S = (1.2, 26.0)  # a whole targeted row's |mean| + sqrt(M2), in units of s (tests/test_envelope_cpu.py holds both pairs to the taps)
+Y_OVER_S = (0.2, 3.9)       # a row of y: max|y| in units of s
+S_IN = 2.0 ** -8
+S_OUT = 2.0 ** -17
+LOW_CURVE = (2.0 ** -6, 2.0 ** -10, 2.0 ** -14)     # the amplitudes of the accuracy curve
+
+
+def flag_at(segment, s, must):
+    """The state the flag MUST have after a call on segment `segment` at amplitude s, or None where the measured bounds leave it open.
+    `must`: the scenario has a whole read outside the float32 section (flagging_sites); without one nothing is claimed.  Up when every
+    whole row is under its floor (the largest bound, with a tenth to spare: the kernels' float32 statistics are within 1e-6 of these),
+    down when none can be within a factor 2 of it.  S_IN and S_OUT are one floor's worth apart for BOTH floors at once, nine binades;
+    this rule also decides the curve's points -- a row segment is down at 2^-6 and up at 2^-14, y is down at 2^-6 and 2^-10 -- which
+    holds kRawFloor inside (the widest rows' smallest bound at 2^-14, the narrowest rows' at 2^-8] and kRawFloorIn inside
+    (max|y| at 2^-17, at 2^-10] ON THE DEVICE; the source text is checked besides (tests/test_envelope_cpu.py)."""
+    if not must:
+        return None
+    (lo, hi), floor = (Y_OVER_S, RAW_FLOOR_IN) if segment == "y" else (BOUND_OVER_S, RAW_FLOOR)
+    if hi * s < 0.9 * floor:
+        return True
+    if lo * s > 2.0 * floor:
+        return False
+    return None
+LowScenario = namedtuple("LowScenario", "name segment s params y_scale tensors sites whole v8_only")
+
+
+def segments(plan):
+    """[(head tensor name, [prefixes whose weight and bias are multiplied by s], [raw-read tensors of the segment])] in stream order."""
+    raw = raw_tensors(plan)
+    segs = [["feature_proj", ["feature_proj"], ["feature_proj"]]]
+    for idx, (kind, i, o) in enumerate(plan["down"]):
+        name = f"down.{idx}"
+        if kind == "res" and i == o:
+            segs[-1][1].append(name + ".res.lin3")
+            segs[-1][2].append(name)
+        elif kind == "lin":
+            segs.append([name, [name + ".lin"], [name]])
+        else:
+            segs.append([name, [name + ".res.lin3", name + ".res.shortcut"], [name]])
+    segs[-1][1] += ["middle.res1.lin3", "middle.res2.lin3"]
+    segs[-1][2].append("middle")
+    for idx, (kind, i, o) in enumerate(plan["up"]):
+        name = f"up.{idx}"
+        assert kind == "lin" or i != o
+        segs.append([name, [name + ".lin"] if kind == "lin" else [name + ".res.lin3", name + ".res.shortcut"], [name]])
+    # the last module's output goes to the final LayerNorm: no raw read, no scenario.  A carried tensor that nothing reads raw does not exist
+    # (every module output but the last is a skip or the next Linear's input); keep the raw-read ones only
+    return [(h, keys, [t for t in ts if t in raw]) for h, keys, ts in segs if any(t in raw for t in ts)]
+
+
+def site_in_v8(plan, site):
+    """Is the Linear at `site` an operator of the narrow run's float32 vector section (one side 8 wide, see v8_section)?"""
+    return bool(v8_section(plan)) and min(O.state_shapes(plan)[site + ".weight"]) == 8
+
+
+def low_scenarios(name, seed, s, only=None):
+    """(plan, base parameters, [LowScenario]) for config `name` at amplitude s: `y`, then one per stream segment (`only`: a set of segment names)."""
+    plan, base = base_params(name, seed)
+    raw, v8, reads = raw_tensors(plan), v8_section(plan), raw_reads(plan)
+    out = []
+
+    def make(seg, keys, tensors, y_scale):
+        p = dict(base)
+        for k in keys:
+            p[k + ".weight"], p[k + ".bias"] = base[k + ".weight"] * s, base[k + ".bias"] * s
+        sites = []
+        for t in tensors:
+            for site, col0 in raw[t].reads:
+                key = site + ".weight"
+                if p[key] is base[key]:
+                    p[key] = base[key].clone()
+                p[key][:, col0:col0 + raw[t].width] /= s
+                if site not in sites:
+                    sites.append(site)
+        whole = tuple(r.site for r in reads if r.site in sites and all(t in tensors for t in r.tensors))
+        out.append(LowScenario(f"{name}:low:{seg}@{s:g}", seg, s, p, y_scale, tuple(tensors), tuple(sites), whole,
+                               all(t in v8 for t in tensors)))
+
+    if only is None or "y" in only:
+        make("y", [], ["y"], s)
+    for head, keys, tensors in segments(plan):
+        if only is None or head in only:
+            make(head, keys, tensors, None)
+    return plan, base, out
+
+
+def flagging_sites(plan, scn, v8):
+    """The sites that must raise the flag when the segment is under the floor: its whole reads, less -- with narrow_valu8 on -- those inside
+    the float32 vector section, which split nothing."""
+    return tuple(st for st in scn.whole if not (v8 and site_in_v8(plan, st)))
+
+
+@functools.lru_cache(maxsize=None)
+def data(name, B, T):
+    """The seeded inputs of tests/test_gpu_envelope.py for config `name` at B rows (read only): cond, start state, injected noise, per-row
+    t, mask, and the training step's y / ts / noise.  Here so that tests/test_envelope_cpu.py can prove the scenarios on the very rows."""
+    from weights import CONFIGS
+    cfg = CONFIGS[name]
+    D, C = cfg["input_dim"], cfg["cond_dim"]
+    g = torch.Generator().manual_seed(100 + B)
+    d = dict(cond=torch.rand(B, C, generator=g), y_T=torch.randn(B, D, generator=g), z=torch.randn(T - 2, B, D, generator=g),
+             t=torch.rand(1, B, generator=g), mask=(torch.rand(B, 1, generator=g) < 0.7).float(),
+             y=torch.rand(B, D, generator=g), ts=torch.randint(0, T, (1, B), generator=g), noise=torch.randn(B, D, generator=g))
+    d["mask"][-1] = 1.0
+    return d
+
+
+def call_inputs(scn, d, T, kind, omega=1.0):
+    """[(network input x [B, D], t [1, B], cond, mask [B, 1])] of every denoiser pass one call of `kind` makes under scenario `scn` on data
+    `d`, from the float32 oracle: both passes of every reverse step, the one forward, or the training step's x_t."""
+    cond, B = d["cond"], d["cond"].shape[0]
+    if kind == "forward":
+        return [(apply_y(scn, d["y_T"]), d["t"], cond, d["mask"])]
+    bufs = O.schedule_buffers(1.0 - O.cosine_betas(T))
+    if kind == "train":
+        sc = scn.y_scale if isinstance(scn, LowScenario) and scn.y_scale is not None else 1.0
+        return [(O.q_sample(bufs, d["y"] * sc, d["ts"], d["noise"] * sc).reshape(B, -1), d["ts"] / T, cond, d["mask"])]
+    out, y = [], apply_y(scn, d["y_T"])
+    with torch.no_grad():
+        for k, i in enumerate(range(T - 1, -1, -1)):
+            t = (torch.full((1, B), i, dtype=torch.int64) / T).to(y.dtype)
+            out += [(y, t, cond, torch.zeros(B, 1)), (y, t, cond, torch.ones(B, 1))]
+            y, _ = O.sample_step(scn.params, scn_plan(scn), bufs, T, i, y, cond, omega, d["z"][k] if i > 1 else 0)
+    return out
+
+
+def scn_plan(scn):
+    from weights import CONFIGS
+    cfg = CONFIGS[scn.name.split(":")[0]]
+    return O.unet_plan(cfg["input_dim"], cfg["proj_dim"], cfg["cond_dim"], cfg["dims"], cfg["n_blocks"])
+
+
 def apply_y(scn, y):
     """`y` with the scenario's element set (the `y` scenario: feature j of the last row becomes A); other scenarios leave it alone."""
+    if isinstance(scn, LowScenario):
+        return y if scn.y_scale is None else y * scn.y_scale
     if scn.y_col is None:
         return y
     y = y.clone()
@@ -166,6 +323,66 @@ def raw_bounds(plan, taps, y):
         m2 = ((x - mean) ** 2).sum(dim=1)
         out[r.site] = (float((mean[:, 0].abs() + m2.sqrt()).max()), float(x.abs().max()))
     return out
+
+
+def raw_bounds_min(plan, taps, y, rows=None):
+    """{site: (min over rows of the quantity the kernel at that site compares with kRawFloor, max over rows of it)} in float64: the row's
+    max|x| for feature_proj, |mean| + sqrt(M2) over the concatenated row elsewhere.  All-zero rows are left out, as the kernels leave them
+    out (a bound of exactly 0 raises nothing); `rows` restricts the survey to a subset of the batch."""
+    out = OrderedDict()
+    for r in raw_reads(plan):
+        x = torch.cat([(y if n == "y" else taps[n]).double() for n in r.tensors], dim=1)
+        if rows is not None:
+            x = x[rows]
+        if r.site == "feature_proj":
+            b = x.abs().amax(dim=1)
+        else:
+            mean = x.mean(dim=1, keepdim=True)
+            b = mean[:, 0].abs() + ((x - mean) ** 2).sum(dim=1).sqrt()
+        b = b[b > 0]
+        out[r.site] = (float(b.min()), float(b.max())) if b.numel() else (float("inf"), 0.0)
+    return out
+
+
+def _merge(acc, bounds):
+    for k, (lo, hi) in bounds.items():
+        a = acc.get(k, (float("inf"), 0.0))
+        acc[k] = (min(a[0], lo), max(a[1], hi))
+    return acc
+
+
+def _padded(x, t, cond, mask):
+    """The rows of one denoiser pass plus a PADDING row -- y = 0, cond = 0, the last row's t and mask: what the ragged last tile of a
+    launch computes in its unused rows, which the kernels bound like any other row."""
+    pad = lambda a: torch.cat([a, torch.zeros(1, a.shape[1], dtype=a.dtype)])       # noqa: E731
+    return pad(x), torch.cat([t, t[:, -1:]], dim=1), pad(cond), torch.cat([mask, mask[-1:]])
+
+
+def survey_sample(p, plan, T, cond, omega, y_T, z):
+    """`raw_bounds_min` over both denoiser passes of every step of the float32 oracle's reverse loop (z: [>= T - 2, B, D]), each pass
+    with a padding row."""
+    bufs, acc, y, B = O.schedule_buffers(1.0 - O.cosine_betas(T)), {}, y_T, cond.shape[0]
+    with torch.no_grad():
+        for k, i in enumerate(range(T - 1, -1, -1)):
+            t = (torch.full((1, B), i, dtype=torch.int64) / T).to(y.dtype)
+            for m in (0.0, 1.0):
+                taps = {}
+                yp, tp, cp, mp = _padded(y, t, cond, torch.full((B, 1), m))
+                O.unet_forward(p, plan, yp, tp, cp, mp, taps=taps)
+                _merge(acc, raw_bounds_min(plan, taps, yp))
+            y, _ = O.sample_step(p, plan, bufs, T, i, y, cond, omega, z[k] if i > 1 else 0)
+    return acc
+
+
+def survey_train(p, plan, T, y, cond, ts, noise, mask):
+    """`raw_bounds_min` of one training forward of the float32 oracle, with a padding row."""
+    bufs = O.schedule_buffers(1.0 - O.cosine_betas(T))
+    x_t = O.q_sample(bufs, y, ts, noise).reshape(y.shape[0], -1)
+    taps = {}
+    xp, tp, cp, mp = _padded(x_t, ts / T, cond, mask)
+    with torch.no_grad():
+        O.unet_forward(p, plan, xp, tp, cp, mp, taps=taps)
+    return raw_bounds_min(plan, taps, xp)
 
 
 def rel(a, b):
