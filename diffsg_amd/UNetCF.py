@@ -152,6 +152,7 @@ class _Native:
         self.chunk_variants = None        # (handle, key of the per-chunk settings), or None: dsg_set_chunk_variants
         self.step_guidance = None         # (handle, the weights as a tuple of floats, their tensor, its version), or None: dsg_set_step_guidance
         self.step_history = None          # (handle, the rows as a tuple of floats, their tensor, its version), or None: dsg_set_step_history
+        self.x0_clip = None               # (handle, the bounds and rows as a tuple of floats, the clip tensor, its version, the taus), or None: dsg_set_xstart_clip
         # ... and DDPM's training calls (setting either moves dsg_generation: a captured step is captured again)
         self.train_law = None             # (handle, the timesteps.TrainLaw), or None: dsg_set_train_law
         self.train_report = None          # (handle, sq tensor, rows tensor), or None: dsg_set_train_report

@@ -122,6 +122,7 @@ def load_test_co(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500.0, bat
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
     entry.check_variants(variants, repeats)
+    plan, variants = entry.clipped(diffusion_model, plan, variants, Y_train)
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)

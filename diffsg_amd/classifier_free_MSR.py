@@ -89,7 +89,7 @@ def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batc
                   sampler="strided", eta=0.0, variants=None):
     """classifier_free_MSR.py:248-298; returns the printed metrics as a dict as well.  `repeats`, `steps` / `sampler` / `eta` and
     `variants`: see `entry`; the objective is the sum rate."""
-    _, _, X_test, Y_test, custom_config = msr_data_load(dataset_path)
+    _, Y_train, X_test, Y_test, custom_config = msr_data_load(dataset_path)
     M, W = custom_config['M'], custom_config['W']
     device = _device()
     diffusion_model = entry.load_checkpoint(build_model(M, custom_config['sfn'] * M, device, T, custom_config, W), ckpt_path, device)
@@ -97,6 +97,7 @@ def load_test_msr(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batc
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
     entry.check_variants(variants, repeats)
+    plan, variants = entry.clipped(diffusion_model, plan, variants, Y_train)
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device) * (custom_config['scaler_max'] - custom_config['scaler_min']) + custom_config['scaler_min']
     Yt = torch.tensor(Y_test, dtype=torch.float32, device=device)

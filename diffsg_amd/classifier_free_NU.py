@@ -97,13 +97,14 @@ def load_test_nu(ckpt_path, dataset_path=DEFAULT_DATASET, T=20, omega=500, batch
                  log=print, repeats=1, steps=None, sampler="strided", eta=0.0, variants=None):
     """classifier_free_NU.py:306-361.  `repeats`, `steps` / `sampler` / `eta` and `variants`: see `entry`; the objective is the best
     rate."""
-    _, _, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
+    _, Y_train, X_test, Y_test, _, custom_config = nu_data_load(dataset_path, width, height)
     K, P_sum = custom_config['K'], custom_config['P_sum']
     device = _device()
     diffusion_model = entry.load_checkpoint(build_model(K, P_sum, device, T, custom_config), ckpt_path, device)
     from .steps import make as make_plan
     plan = make_plan(diffusion_model, steps, sampler, eta)
     entry.check_variants(variants, repeats)
+    plan, variants = entry.clipped(diffusion_model, plan, variants, Y_train)
     X = torch.tensor(X_test, dtype=torch.float32)
     Xt = X.to(device).clone()
     Xt[:, 0::2] *= width

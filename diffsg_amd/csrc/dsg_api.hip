@@ -19,6 +19,7 @@
 #include "dsg_ppo.hpp"
 #include "dsg_gd.hpp"
 #include "dsg_multistep.hpp"
+#include "dsg_clip.hpp"
 #include "dsg_own.hpp"
 #include "../../include/diffsg.h"
 
@@ -232,6 +233,42 @@ int dsg_set_step_history(dsg_handle* h, const float* hist_host, int n) {
     }
     HIPCK(hipMemcpy(h->hist_dev, hist_host, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice));
     h->hist_n = n;
+    return 0;
+}
+
+int dsg_set_xstart_clip(dsg_handle* h, const float* lo_host, const float* hi_host, int D, const float* x0_host, int n) {
+    if (!h) return fail("null handle");
+    if (n < 0) return fail("dsg_set_xstart_clip: n = %d is negative", n);
+    if (!lo_host || !hi_host || n == 0) { h->clip_n = 0; return 0; }     // nothing is overwritten: an enqueued call keeps reading the buffers
+    if (D != h->d.input_dim) return fail("dsg_set_xstart_clip: D = %d bounds, the net has input_dim = %d", D, h->d.input_dim);
+    if (!x0_host) return fail("dsg_set_xstart_clip: null pointer to the rows {s, ia, a, is}");
+    for (int f = 0; f < D; ++f) {
+        if (lo_host[f] != lo_host[f] || hi_host[f] != hi_host[f])
+            return fail("dsg_set_xstart_clip: feature %d has the bounds [%g, %g]: a bound is a number or an infinity, not a NaN", f, (double)lo_host[f],
+                        (double)hi_host[f]);
+        if (lo_host[f] > hi_host[f])
+            return fail("dsg_set_xstart_clip: feature %d has lo = %g above hi = %g", f, (double)lo_host[f], (double)hi_host[f]);
+    }
+    for (int j = 0; j < 4 * n; ++j)
+        if (!(x0_host[j] > 0.f && x0_host[j] <= 3.402823466e38f))     // NaN fails the first comparison, +inf the second
+            return fail("dsg_set_xstart_clip: row %d holds %g: the rows {s, ia, a, is} are finite and > 0", j / 4, (double)x0_host[j]);
+    DeviceGuard dg(h);
+    // an enqueued call may still read the old bounds and rows; the step graphs hold neither the buffers nor the values and stay
+    HIPCK(hipDeviceSynchronize());
+    // staged in buffers of their own and swapped in whole (D + n floats, on a call that synchronises anyway): a failed allocation or copy
+    // leaves the clip the handle holds as it was
+    DevBuf<ClipParams> call;
+    DevBuf<float> bounds, rows;
+    if (!h->clip_call) HIPCK(call.alloc(1));
+    HIPCK(bounds.alloc((size_t)2 * D));
+    HIPCK(rows.alloc((size_t)4 * n));
+    HIPCK(hipMemcpy(bounds, lo_host, (size_t)D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(bounds.get() + D, hi_host, (size_t)D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(rows, x0_host, (size_t)4 * n * sizeof(float), hipMemcpyHostToDevice));
+    if (call) h->clip_call = std::move(call);
+    h->clip_bounds = std::move(bounds);
+    h->clip_rows = std::move(rows);
+    h->clip_n = n;
     return 0;
 }
 

@@ -114,8 +114,10 @@ constexpr int kWgForkMinTiles = 1024;
 constexpr int kStepRunGraphs = 6;
 // the kinds of a step: the plain one, and under a guidance schedule (dsg_set_step_guidance) the two-pass step with the
 // scheduled update and the one-pass (unguided) step; and the same three with the history form of the update (dsg_set_step_history,
-// k_update_hist, k_update_hist_sched), STEP_HIST + the kind without a history
-enum StepKind { STEP_PLAIN = 0, STEP_SCHED = 1, STEP_ONEPASS = 2, STEP_HIST = 3, STEP_HIST_SCHED = 4, STEP_HIST_ONEPASS = 5, kStepKinds = 6 };
+// k_update_hist, k_update_hist_sched), STEP_HIST + the kind without a history; and each of the six with the clip form of its
+// update (dsg_set_xstart_clip, DESIGN.md 20: dsg_clip.hpp), STEP_CLIP + the kind without a clip.  kind % 3 == STEP_ONEPASS: one denoiser pass
+enum StepKind { STEP_PLAIN = 0, STEP_SCHED = 1, STEP_ONEPASS = 2, STEP_HIST = 3, STEP_HIST_SCHED = 4, STEP_HIST_ONEPASS = 5, STEP_CLIP = 6,
+                kStepKinds = 12 };
 struct StepGraphs {
     GraphExec exec[kStepKinds][1 + kStepRunGraphs];
     int rows = -1, chunks = -1, chunk_rows = -1;    // chunk_rows: the renorm kernels capture the segment size as an argument
@@ -224,6 +226,11 @@ struct dsg_handle {
     // and the workspace tensor fw.hist, never this buffer: k_set_guidance writes its address into `hist_call` per call.
     DevBuf<float> hist_dev; int hist_n = 0, hist_cap = 0;
     DevBuf<const float*> hist_call;
+    // dsg_set_xstart_clip: the bounds lo / hi [D] of the predicted solution and one row {s, ia, a, is} per step index of a sampling call
+    // (DESIGN.md 20); clip_n == 0: none held.  The buffers are kept when the setting is removed and replaced whole by the next set.  The
+    // step graphs of the clip kinds hold `clip_call` (one block, allocated once), never these buffers: k_set_clip writes their addresses per call.
+    DevBuf<float> clip_bounds, clip_rows; int clip_n = 0;
+    DevBuf<ClipParams> clip_call;
     double* renorm_stats = nullptr;              // dsg_set_renorm_hook: caller's 3 doubles (device, not owned), reduced across ranks by `renorm_fn`
     void (*renorm_fn)(void*) = nullptr; void* renorm_user = nullptr;
     int device = 0;              // the device that was current in dsg_create: the settings / status entry points select it themselves

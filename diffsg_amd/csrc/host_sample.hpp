@@ -8,8 +8,9 @@ namespace {
 // per-chunk settings (`var`, chunk variants) or without, and the renorm partial sums -- one call: the handle's two partial rows; chunked:
 // [chunks][kRedBlocks] twice, one grid row per chunk.  `sched`: the handle holds a guidance schedule (dsg_set_step_guidance): the update
 // is the scheduled form, and a step is two-pass or one-pass (StepKind).  `hist`: the handle holds a step history (dsg_set_step_history):
-// the update is the history form (dsg_multistep.hpp), never together with `var`.
-struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; bool sched; bool hist; };
+// the update is the history form (dsg_multistep.hpp), never together with `var`.  `clip`: the handle holds an x0 clip (dsg_set_xstart_clip):
+// the update is the clip form of whichever of those it would be (dsg_clip.hpp).
+struct StepForm { int chunks; size_t chunk_n; bool var; double *p1, *p2; bool sched; bool hist; bool clip; };
 
 // The two contexts of a call: ctx[0] two passes (unconditional tiles first), ctx[1] the one pass of an unguided step, with the resident
 // table set of each (dsg_handle::tabs).  Only a call whose schedule has a zero builds and prepares ctx[1].
@@ -37,7 +38,15 @@ int enqueue_step(dsg_handle* h, const StepCtxs& cs, bool one_pass, const UpdateA
     UpdateArgs ua = u;
     ua.record_y = renorm ? 0 : 1;
     const float* const* gpp = h->guid_call;
-    if (f.hist && f.sched) hipLaunchKernelGGL(k_update_hist_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp, h->fw.hist.get(), (const float* const*)h->hist_call);
+    const float* const* hpp = h->hist_call;
+    const ClipParams* clpp = h->clip_call;
+    if (f.clip && f.hist && f.sched) hipLaunchKernelGGL(k_update_clip_hist_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp, h->fw.hist.get(), hpp, clpp);
+    else if (f.clip && f.hist) hipLaunchKernelGGL(k_update_clip_hist, dim3(ublocks), dim3(256), 0, s, ua, h->fw.hist.get(), hpp, clpp);
+    else if (f.clip && f.var && f.sched) hipLaunchKernelGGL(k_update_clip_var_sched, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, gpp, clpp);
+    else if (f.clip && f.var) hipLaunchKernelGGL(k_update_clip_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, clpp);
+    else if (f.clip && f.sched) hipLaunchKernelGGL(k_update_clip_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp, clpp);
+    else if (f.clip) hipLaunchKernelGGL(k_update_clip, dim3(ublocks), dim3(256), 0, s, ua, clpp);
+    else if (f.hist && f.sched) hipLaunchKernelGGL(k_update_hist_sched, dim3(ublocks), dim3(256), 0, s, ua, gpp, h->fw.hist.get(), (const float* const*)h->hist_call);
     else if (f.hist) hipLaunchKernelGGL(k_update_hist, dim3(ublocks), dim3(256), 0, s, ua, h->fw.hist.get(), (const float* const*)h->hist_call);
     else if (f.var && f.sched) hipLaunchKernelGGL(k_update_var_sched, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call, gpp);
     else if (f.var) hipLaunchKernelGGL(k_update_var, dim3(ublocks), dim3(256), 0, s, ua, (const VarParams*)h->var_call);
@@ -85,7 +94,9 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         return fail("dsg_sample: the handle's guidance schedule (dsg_set_step_guidance) has %d weights, the call has T = %d", h->guid_n, T);
     if (h->hist_n && T != h->hist_n)
         return fail("dsg_sample: the handle's step history (dsg_set_step_history) has %d rows, the call has T = %d", h->hist_n, T);
-    const bool sched = h->guid_n > 0, hist = h->hist_n > 0;
+    if (h->clip_n && T != h->clip_n)
+        return fail("dsg_sample: the handle's x0 clip (dsg_set_xstart_clip) has %d rows, the call has T = %d", h->clip_n, T);
+    const bool sched = h->guid_n > 0, hist = h->hist_n > 0, clip = h->clip_n > 0;
     // step k of the call (step index T-1-k) is unguided: one denoiser pass
     auto unguided = [&](int k) { return sched && h->guid_host[(size_t)(T - 1 - k)] == 0.f; };
     bool any_one_pass = false;
@@ -162,6 +173,10 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     }
     if (sched) hipLaunchKernelGGL(k_set_guidance, dim3(1), dim3(64), 0, s, h->guid_call.get(), (const float*)h->guid_dev);
     if (hist) hipLaunchKernelGGL(k_set_guidance, dim3(1), dim3(64), 0, s, h->hist_call.get(), (const float*)h->hist_dev);   // (the same one-word store)
+    if (clip) {
+        const ClipParams clp{h->clip_bounds.get(), h->clip_bounds.get() + h->d.input_dim, h->clip_rows.get(), h->d.input_dim};
+        hipLaunchKernelGGL(k_set_clip, dim3(1), dim3(64), 0, s, h->clip_call.get(), clp);
+    }
 
     StepCtxs cs{{RunCtx{B, 2, tpp, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true},
                  RunCtx{B, 1, 0, h->fw.ywork, h->fw.eps, h->step_dev, nullptr, false, true}}};
@@ -178,7 +193,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
     }
     if (prepare_fused(h, cs.ctx[0], s)) return 1;
     const StepForm form{chunks, chunk_n, var, chunks > 1 ? h->red_chunks : h->red,
-                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks, sched, hist};
+                        chunks > 1 ? h->red_chunks + (size_t)chunks * kRedBlocks : h->red + kRedBlocks, sched, hist, clip};
     UpdateArgs u;
     u.eps = h->fw.eps; u.y = h->fw.ywork; u.cp = h->call_dev; u.step_ptr = h->step_dev; u.n = n; u.record_y = 0;
 
@@ -209,7 +224,10 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
         // captured lazily: only the run lengths a call replays (a one-off batch size pays for its own decomposition, not for
         // 64 steps of nodes)
         // under a step history the same three with the history form of the update (STEP_HIST ...): the rows {m, p, q} are read on the device
-        auto kind_of = [&](int k) { return (hist ? (int)STEP_HIST : 0) + (!sched ? STEP_PLAIN : unguided(k) ? STEP_ONEPASS : STEP_SCHED); };
+        // under an x0 clip the same six with the clip form of the update (STEP_CLIP ...): bounds and rows are read on the device
+        auto kind_of = [&](int k) {
+            return (clip ? (int)STEP_CLIP : 0) + (hist ? (int)STEP_HIST : 0) + (!sched ? STEP_PLAIN : unguided(k) ? STEP_ONEPASS : STEP_SCHED);
+        };
         auto graph_of = [&](int kind, int variant) -> int {
             GraphExec& ge = G.exec[kind][variant];
             if (ge) return 0;
@@ -218,7 +236,7 @@ int sample_impl(dsg_handle* h, const float* cond, const float* y_T, const float*
             HIPCK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = 0;
             for (int k = 0; k < run && !rc; ++k)
-                rc = enqueue_step(h, cs, kind == STEP_ONEPASS || kind == STEP_HIST_ONEPASS, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
+                rc = enqueue_step(h, cs, kind % 3 == STEP_ONEPASS, u, form, variant == 0, h->cap_stream, nullptr, /*use_hook=*/false);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc) return 1;
             if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));

@@ -102,7 +102,8 @@ class DDPMCore(nn.Module):
                       `noise` is then (K-2, B, D) and the recorded trajectory (B, K*D).  None: all T trained steps.  A plan with
                       `guidance` (steps.with_guidance) guides step j with omega * g_j and runs the conditional denoiser pass alone
                       where g_j == 0 (the recorded eps of such a step is that pass's output); DESIGN.md 16.  A plan with `history`
-                      (steps.dpmpp_2m, steps.with_history) runs the update with the history term; DESIGN.md 18.
+                      (steps.dpmpp_2m, steps.with_history) runs the update with the history term; DESIGN.md 18.  A plan with `clip`
+                      (steps.with_clip) keeps every step's predicted solution inside per-feature bounds; DESIGN.md 20.
         """
         K = self._plan_steps(plan, cond, noise)
         if not cond.is_cuda:
@@ -185,6 +186,12 @@ class DDPMCore(nn.Module):
             from .steps import check_history
             try:
                 check_history(plan.history, K)
+            except ValueError as e:
+                raise ValueError(f"step plan: {e}") from None
+        if plan.clip is not None:
+            from .steps import check_clip
+            try:
+                check_clip(plan.clip, self.model.cfg["input_dim"])
             except ValueError as e:
                 raise ValueError(f"step plan: {e}") from None
         self._check_noise(noise, K, cond.shape[0], f" for a plan of {K} steps")
@@ -294,6 +301,38 @@ class DDPMCore(nn.Module):
                 _lib.check(_lib.lib().dsg_set_step_history(hd, arr, len(key) // 3))
         nat.step_history = (hd, key, hist, hist._version)
 
+    def _use_clip(self, hd, plan, dev):
+        """Make handle `hd` hold the clip of `plan` (None, or a plan without one: none) with the rows {s, ia, a, is} of the plan's trained
+        steps, as `_use_history` holds the rows: repeated calls with the same bounds on the same steps set nothing (setting them
+        synchronises the device), a plan without a clip after one with it removes it."""
+        import ctypes
+        nat = self.model._native
+        held = nat.x0_clip                               # (handle, bounds and rows, the clip tensor, its version, the taus)
+        if held is not None and held[0] != hd:
+            held = None
+        clip = None if plan is None else plan.clip
+        if clip is None:
+            if held is not None:
+                _lib.check(_lib.lib().dsg_set_xstart_clip(hd, None, None, 0, None, 0))
+                nat.x0_clip = None
+            return
+        taus = tuple(plan.taus)
+        acp = self.alphas_cumprod
+        stamp = (clip._version, acp.data_ptr(), acp._version)
+        if held is not None and held[2] is clip and held[3] == stamp and held[4] == taus:      # the same tensor on the same steps, unchanged
+            return
+        from .steps import x0_rows
+        D = self.model.cfg["input_dim"]
+        c = clip.detach().cpu().to(torch.float32)
+        lo, hi = c[0].expand(D).tolist(), c[1].expand(D).tolist()
+        rows = x0_rows(self, taus).reshape(-1).tolist()
+        key = (tuple(lo), tuple(hi), tuple(rows))
+        if held is None or held[1] != key:
+            with torch.cuda.device(dev):          # a refused or failed call leaves what the handle holds, and this record of it, unchanged
+                _lib.check(_lib.lib().dsg_set_xstart_clip(hd, (ctypes.c_float * D)(*lo), (ctypes.c_float * D)(*hi), D,
+                                                      (ctypes.c_float * len(rows))(*rows), len(taus)))
+        nat.x0_clip = (hd, key, clip, stamp, taus)
+
     def _resolve_variants(self, variants, cond, noise):
         """[(omega, plan)] of a list of variants with `None` plans replaced by the identity plan (all T trained steps, the trained table's
         own rows, min(T, 4) renorm steps), and the step count K they share -- after the checks that need no device: every plan passes
@@ -326,6 +365,9 @@ class DDPMCore(nn.Module):
             if not _same_guidance(plan.guidance, first.guidance):
                 raise ValueError(f"variant {k} has another guidance schedule than variant 0: the variants of one call share `guidance` "
                                  "(the number of denoiser passes is per launch, not per chunk)")
+            if not _same_clip(plan.clip, first.clip):
+                raise ValueError(f"variant {k} has another clip than variant 0: the variants of one call share `clip` (steps.with_clip), as "
+                                 "they share the guidance schedule")
             out.append((float(omega), plan))
         return out, len(out[0][1].taus)
 
@@ -352,6 +394,7 @@ class DDPMCore(nn.Module):
                 self._use_plan(hd, plan0, dev)
         self._use_guidance(hd, plan0.guidance, dev)           # the schedule the variants share
         self._use_history(hd, None, dev)                      # variants have none (_resolve_variants)
+        self._use_clip(hd, plan0, dev)                        # the clip the variants share
         # the distinct coefficient tensors, stacked once
         coefs, table = [], []
         for _, p in chunks:
@@ -392,6 +435,7 @@ class DDPMCore(nn.Module):
         coef = self._use_plan(hd, plan, dev)
         self._use_guidance(hd, None if plan is None else plan.guidance, dev)
         self._use_history(hd, None if plan is None else plan.history, dev)
+        self._use_clip(hd, plan, dev)
         flags = 2 if profile else (0 if use_graph else 1)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().dsg_sample_rec(hd, _lib.ptr(cond), _lib.ptr(y_T), zptr, seed, float(omega), _lib.ptr(coef), T,
@@ -464,6 +508,7 @@ class DDPMCore(nn.Module):
                 coef = self._use_plan(hd, plan, dev)
                 self._use_guidance(hd, None if plan is None else plan.guidance, dev)
                 self._use_history(hd, None if plan is None else plan.history, dev)
+                self._use_clip(hd, plan, dev)
             else:
                 coef = self._use_variants(hd, variants, dev)      # [tables][K][4]; `omega` is not read by the call
             with torch.cuda.device(dev):
@@ -940,6 +985,17 @@ def _same_guidance(a, b):
     if a is None or b is None:
         return a is b
     return a is b or (tuple(a.shape) == tuple(b.shape) and torch.equal(a.cpu(), b.cpu()))
+
+
+def _same_clip(a, b):
+    """The same bounds once spread over the features: a scalar pair [2, 1] equals the same values given per feature [2, D]."""
+    if a is None or b is None or a is b:
+        return a is b
+    a, b = a.detach().cpu(), b.detach().cpu()
+    if a.shape[1] != b.shape[1] and 1 not in (a.shape[1], b.shape[1]):
+        return False
+    D = max(a.shape[1], b.shape[1])
+    return torch.equal(a.expand(2, D), b.expand(2, D))
 
 
 def _is_trained_grid(plan, T):

@@ -12,10 +12,15 @@ The sampler options of `load_test_msr`, `load_test_co` and `load_test_nu`, beyon
             A plan of a variant may carry a guidance schedule (`steps.with_guidance(plan_or_model, g)`, DESIGN.md 16: step j guided with
             omega * g_j, one denoiser pass where g_j == 0); the variants of one call share it.  The entry points have no keyword of their
             own for it: their signatures are pinned.
+  clip      no keyword either: `with steps.clipping(lo, hi):` or `with steps.clipping(margin=m):` around the call.  Inside
+            the context the single-setting plan (the identity plan for `steps=None`) and every variant plan without a clip of its own
+            sample under the clip; with `margin` the bounds are `steps.clip_bounds` of the loader's own training labels.
 """
 from __future__ import annotations
 
 import torch
+
+from .steps import clipping     # `entry.clipping` is `steps.clipping`: the context the entry points read through `clipped`
 
 
 def device():
@@ -33,6 +38,26 @@ def load_checkpoint(model, ckpt_path, device):
 def check_variants(variants, repeats):
     if variants is not None and repeats < 2:
         raise ValueError("variants are settings of repeated sampling: pass repeats >= 2")
+
+
+def clipped(model, plan, variants, Y_train):
+    """`plan` and `variants` of a `load_test_*` call under the enclosing `steps.clipping()` context, unchanged outside one: the
+    single-setting plan (the identity plan for None) with the context's clip, and every variant plan that carries none with it too.
+    `Y_train`: the loader's training labels, read for `clipping(margin=...)` alone."""
+    from . import steps
+    bounds = steps.active_clip(Y_train)
+    if bounds is None:
+        return plan, variants
+    ident = steps.with_clip(model, *bounds)        # built once: the variants without a plan share its tensors
+    plan = ident if plan is None else steps.with_clip(plan, *bounds)
+    if variants is not None:
+        clip = plan.clip
+        def one(p):
+            if p is None:
+                return ident
+            return p if p.clip is not None else steps.StepPlan(p.taus, p.t, p.coef, p.renorm_steps, p.guidance, p.history, clip)
+        variants = [(o, one(p)) for o, p in variants]
+    return plan, variants
 
 
 def sample_in_batches(model, X, omega, batch_size, plan=None):
